@@ -2,6 +2,7 @@
 """Benchmark of the DGR inference hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--pairs-per-step B] [--streams S] [--total-pairs P]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (FCGF x2 -> 1-NN -> 6-D inputs -> 6-D inlier net -> gate ->
 weighted Procrustes -> SE(3) refinement; `dgr_register_batch`) over synthetic 3DMatch-shaped pairs
@@ -20,6 +21,11 @@ With N > 1 the script runs one process per GPU under `torch.distributed.run` (it
 under the launcher when started plainly with `--gpus N`); the weights come from rank 0 by ONE RCCL
 broadcast, the results are gathered on rank 0, no collective on the data path.
 
+A plain run sets up, warms up, times the K steps and prints the result line (`value` in pairs/s, `ms_per_step`);
+`--dump-outputs DIR` also writes what the last timed step returned.  `--full` adds, after the timed steps, everything
+beyond the headline: the profiled re-runs behind the `roofline` / `roofline_detail` / `stage_ms_per_batch` / `layers_*`
+fields, the oracle parity of one pair per stream, the CPU baseline and the exact-f32 leg.
+
 Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for the definition of every field.
 """
 import argparse
@@ -30,6 +36,7 @@ import subprocess
 import sys
 import threading
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -54,6 +61,13 @@ _T0 = time.time()
 def log(msg):
     if int(os.environ.get('RANK', 0)) == 0:
         print(f'[bench +{time.time() - _T0:6.1f}s] {msg}', file=sys.stderr, flush=True)
+
+
+def dtype_label(split):
+    """The result line's `dtype`: split = the conv kernels issue on the f16 pipe (two f16 pieces per f32 operand)."""
+    return (('f32 results via 2 x f16 split operands (3 f16 MFMA products per MAC, f32 accumulate); k = 1 convs, '
+             'kNN re-evaluation and registration in exact f32, SVD in f64') if split else
+            'f32 (v_mfma_f32_*_f32 on the f32 operands: DGR_EXACT_F32=1); SVD in f64')
 
 
 def cfg_label(args):
@@ -318,11 +332,12 @@ def main():
     ap.add_argument('--voxel', type=float, default=0.05)
     ap.add_argument('--kind', default='indoor', choices=['indoor', 'outdoor'])
     ap.add_argument('--conv1-ks', type=int, default=7)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true', help='skip the oracle comparison of pair 0 (about 30 s of CPU)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-parity', action='store_true', help='--full: skip the oracle comparison of one pair per stream (about '
+                    '30 s of CPU)')
     ap.add_argument('--no-refine', action='store_true', help='ablation: stop after weighted Procrustes')
-    ap.add_argument('--no-exact-leg', action='store_true', help='skip the short DGR_EXACT_F32=1 leg (a child process after the '
-                    'timed region; it only runs together with the parity leg)')
+    ap.add_argument('--no-exact-leg', action='store_true', help='--full: skip the short DGR_EXACT_F32=1 leg (a child process after '
+                    'the timed region; it only runs together with the parity leg)')
     ap.add_argument('--from-host', action='store_true', help='PCIe-inclusive variant (NOT the headline): every step '
                     'starts from the raw float64 host points (H2D copy + GPU voxelisation inside the timed region)')
     ap.add_argument('--cu-shares', type=int, default=0, help='number of equal shares of the compute units (2 or 4) the contexts are '
@@ -340,6 +355,12 @@ def main():
                     'step before it (1 = every step re-registers the same pairs)')
     ap.add_argument('--dump-results', default=None, help='rank 0 writes the gathered per-pair results (pair ids, T, status, stats) '
                     'of the last timed step to this .npz (tests)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='rank 0 writes what the timed path returned in the '
+                    'last timed step, every pair ordered by pair id, as float64 DIR/<name>.npy: pair_ids, T [P,4,4], status [P], '
+                    'stats [P,4] (iterations, loss, break count, sum of weights)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also measure and check everything beyond the '
+                    'headline: the profiled re-runs and the roofline / per-kernel accounting, the oracle parity of one pair per '
+                    'stream, the CPU baseline and the exact-f32 leg (each still subject to its --no-* switch)')
     ap.add_argument('--launch-check', action='store_true', help='CPU-only check of the multi-rank plumbing')
     args = ap.parse_args()
 
@@ -415,14 +436,17 @@ def main():
     log('checkpoint ready')
 
     # ---- which pairs does this rank register? --------------------------------------------------
-    vox_cache = {}
+    vox_cache, raw_cache = {}, {}
+    # set-up's host-side work (seeded synthetic pairs, teacher-forced matches) on a few threads; each call seeds its own
+    # generator, so the inputs are those of a serial set-up
+    host_pool = ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1) // world))
 
     def voxelised(seed, keep=True):
         """Pair `seed`: raw points (kept only for --from-host), voxelised tensors on the device, ground-truth pose.
         `keep=False`: not cached (the cost pass of the strong-scaling mode looks at pairs this rank may not get)."""
         if seed in vox_cache:
             return vox_cache[seed]
-        a, b, Tg = synth.synth_pair(seed, n_raw=args.n_raw, kind=args.kind)
+        a, b, Tg = raw_cache.pop(seed) if seed in raw_cache else synth.synth_pair(seed, n_raw=args.n_raw, kind=args.kind)
         xa, ca, _ = ops.voxelize(a, args.voxel, 0, device)
         xb, cb, _ = ops.voxelize(b, args.voxel, 0, device)
         rec = (a if args.from_host else None, b if args.from_host else None, Tg, xa, ca, xb, cb)
@@ -448,6 +472,7 @@ def main():
         # weak scaling: S x B own pairs per rank and step, R distinct sets of them taken in turn
         R = max(1, args.rotate_sets)
         my_pairs = [rank * S * B * R + i for i in range(S * B * R)]
+        raw_cache.update(zip(my_pairs, host_pool.map(lambda s_: synth.synth_pair(s_, n_raw=args.n_raw, kind=args.kind), my_pairs)))
     # batches of B pairs, dealt over the S streams (weak mode: stream w holds batches w, w + S, ...: one per set)
     batches = [my_pairs[i:i + B] for i in range(0, len(my_pairs), B)]
     per_stream = [batches[w::S] for w in range(S)]
@@ -497,18 +522,19 @@ def main():
                 self.net_s = time.perf_counter() - t_n     # state dict -> the kernels' operand layouts in HBM (or: share them)
                 self.batches = []
                 for ids in self.batch_ids:
-                    x0, c0, x1, c1, off0, off1, ovr = [], [], [], [], [0], [0], []
+                    x0, c0, x1, c1, off0, off1, hosts = [], [], [], [], [0], [0], []
                     for q, seed in enumerate(ids):
                         a, b, Tg, xa, ca, xb, cb = voxelised(seed)
                         ca, cb = ca.clone(), cb.clone()
                         ca[:, 0] = q; cb[:, 0] = q
-                        # harness-only override (DESIGN.md "Synthetic workload"): untrained weights give ~0 %
-                        # correct matches, so a share of the 1-NN results is replaced by ground-truth matches
-                        # AFTER the search ran
-                        g = synth.gt_correspondences(xa.cpu().numpy(), xb.cpu().numpy(), Tg, args.voxel, seed=seed)
-                        ovr.append(np.where(g >= 0, g + off1[-1], -1))
+                        hosts.append((xa.cpu().numpy(), xb.cpu().numpy(), Tg, seed))
                         x0.append(xa); c0.append(ca); x1.append(xb); c1.append(cb)
                         off0.append(off0[-1] + len(xa)); off1.append(off1[-1] + len(xb))
+                    # harness-only override (DESIGN.md "Synthetic workload"): untrained weights give ~0 %
+                    # correct matches, so a share of the 1-NN results is replaced by ground-truth matches
+                    # AFTER the search ran
+                    gts = host_pool.map(lambda h: synth.gt_correspondences(h[0], h[1], h[2], args.voxel, seed=h[3]), hosts)
+                    ovr = [np.where(g >= 0, g + off1[q], -1) for q, g in enumerate(gts)]
                     bt = {'ids': ids, 'C0': torch.cat(c0), 'X0': torch.cat(x0), 'C1': torch.cat(c1), 'X1': torch.cat(x1),
                           'off0': off0, 'off1': off1, 'ovr': torch.from_numpy(np.concatenate(ovr)).to(device),
                           'forced': None, 'raw': [(vox_cache[s][0], vox_cache[s][1]) for s in ids]}
@@ -585,6 +611,7 @@ def main():
     workers = [Worker(w, ids) for w, ids in enumerate(per_stream) if ids]
     for w in workers:
         w.prepare(shared_with=None if (w is workers[0] or os.environ.get('DGR_BENCH_PRIVATE_WEIGHTS')) else workers[0])
+    host_pool.shutdown()
     # pairs this rank registers per step
     n_local = sum(len(w.batch_ids[0]) if rotate else sum(len(ids) for ids in w.batch_ids) for w in workers)
     b0 = workers[0].batches[0]
@@ -624,17 +651,18 @@ def main():
     startup = {'checkpoint_broadcast': float(st[0]), 'weights_to_operand_layouts': float(st[1]),
                'weights_prepared_on_device_this_rank': bool(getattr(w0.dgr.inlier_model._handle(), 'created_on_device', False))}
     _lib.use_ctx(w0.ctx)
-    # outputs of the LAST call of stream 0 (the last batch of the last timed step), before anything else runs there
-    last_bt = w0.last_bt
-    with torch.cuda.stream(w0.stream):
-        hip_out = {k: ops.batch_output(device, k).cpu().numpy() for k in ('idx1', 'logit', 'F0', 'F1')}
-    # ... and of every other stream's last call (the parity leg checks one pair per stream)
-    stream_outs = [(w0.last_bt, hip_out)]
-    for w in workers[1:]:
-        _lib.use_ctx(w.ctx)
-        with torch.cuda.stream(w.stream):
-            stream_outs.append((w.last_bt, {k: ops.batch_output(device, k).cpu().numpy() for k in ('idx1', 'logit', 'F0', 'F1')}))
-    _lib.use_ctx(w0.ctx)
+    stream_outs = []
+    if args.full:
+        # outputs of the LAST call of stream 0 (the last batch of the last timed step), before anything else runs there
+        with torch.cuda.stream(w0.stream):
+            hip_out = {k: ops.batch_output(device, k).cpu().numpy() for k in ('idx1', 'logit', 'F0', 'F1')}
+        # ... and of every other stream's last call (the parity leg checks one pair per stream)
+        stream_outs = [(w0.last_bt, hip_out)]
+        for w in workers[1:]:
+            _lib.use_ctx(w.ctx)
+            with torch.cuda.stream(w.stream):
+                stream_outs.append((w.last_bt, {k: ops.batch_output(device, k).cpu().numpy() for k in ('idx1', 'logit', 'F0', 'F1')}))
+        _lib.use_ctx(w0.ctx)
     T = np.concatenate([r[0] for w in workers for r in w.results])
     status = np.concatenate([r[1] for w in workers for r in w.results])
     stats = np.concatenate([r[2] for w in workers for r in w.results])
@@ -643,6 +671,81 @@ def main():
     gathered_ids = ddist.gather_results(np.tile(np.eye(4), (len(ids_local), 1, 1)) * np.asarray(ids_local)[:, None, None],
                                         np.zeros(len(ids_local), np.int32), np.zeros((len(ids_local), 4), np.float32),
                                         dst=0, device=coll_dev)
+    cus_timed = w0.cus        # compute units a launch of the timed configuration ran on (None: all of them)
+    if rank == 0:
+        T_all, status_all, stats_all = gathered
+        ids_all = [int(round(v)) for v in gathered_ids[0][:, 0, 0]]
+        if args.dump_results:
+            np.savez(args.dump_results, ids=np.asarray(ids_all), T=T_all, status=status_all, stats=stats_all)
+        if args.dump_outputs:
+            # what the callers of the timed path (register_voxelized, one per batch) received in the last timed step
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            order = np.argsort(ids_all, kind='stable')
+            for name, a in (('pair_ids', np.asarray(ids_all)), ('T', T_all), ('status', status_all), ('stats', stats_all)):
+                np.save(os.path.join(args.dump_outputs, name + '.npy'), np.asarray(a)[order].astype(np.float64))
+            log(f'outputs of the last timed step written to {args.dump_outputs}')
+        te, re = [], []
+        for p, seed in enumerate(ids_all):
+            if (int(status_all[p]) & 0xff) in (0, 3):   # estimated by the network path or by the safeguard RANSAC (flags masked)
+                Tg = vox_cache[seed][2] if seed in vox_cache else synth.synth_pair(seed, n_raw=args.n_raw, kind=args.kind)[2]
+                te.append(float(np.linalg.norm(T_all[p][:3, 3] - Tg[:3, 3])))
+                c = (np.trace(T_all[p][:3, :3].T @ Tg[:3, :3]) - 1) / 2
+                re.append(float(np.degrees(np.arccos(np.clip(c, -1, 1)))))
+        nb = len(b0['ids'])
+        ncu_all = torch.cuda.get_device_properties(device).multi_processor_count
+        pairs_per_step = (args.total_pairs or world * n_local)
+        # the kernels issue on the f16 pipe (split operands) unless DGR_EXACT_F32 is set (net.hip, conv_os.hip); --full
+        # reads it off the dominant kernel's name instead
+        split = 'DGR_EXACT_F32' not in os.environ
+        out = {
+            'metric': 'pair registrations/sec (FCGF x2 + 1-NN + 6-D inlier net + gate + weighted Procrustes + SE(3) refinement'
+                      + (' + ICP' if args.full_register else '') + (', safeguard RANSAC forced' if args.force_safeguard else '') + ')',
+            'value': pairs_per_step * args.steps / elapsed, 'unit': 'pairs/s', 'n_gpus': world,
+            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
+            'higher_is_better': True, 'scaling': 'strong' if args.total_pairs else 'weak', 'vs_baseline': None,
+            'dtype': dtype_label(split),
+            'data': 'synthetic 3DMatch-shaped pairs, seeded synthetic weights, teacher-forced matches (20% GT) and inlier logits'
+                    + ('; PCIe-inclusive: raw host points -> H2D -> voxelisation inside the timed region' if args.from_host else ''),
+            'config': {'workload': f'{pairs_per_step} pairs/step ({world} GPU(s) x {len(workers)} stream(s) x batches of {B}), '
+                                   f'{args.n_raw} raw pts/fragment, {args.kind}, voxel {args.voxel}, conv1 k={args.conv1_ks} '
+                                   f'({cfg_label(args)})',
+                       'streams_per_gpu': len(workers),
+                       'cu_partition': (f'{len(workers)} contexts on {partition} shares of {cus_timed} of {ncu_all} compute units each '
+                                        '(CU-masked streams, dgr_ctx_create_partition_stream)') if cus_timed else 'none (plain streams)',
+                       'warmup_steps_run': workers[0].warmup_steps,
+                       # weight sets resident per GPU (the streams share one: dgr_net_share) and their bytes
+                       'weight_sets_per_gpu': (1 if workers[0].dgr.inlier_model._handle().sharers == len(workers) else len(workers)),
+                       'weight_bytes_per_set': int(workers[0].dgr.fcgf_model._handle().param_bytes
+                                                   + workers[0].dgr.inlier_model._handle().param_bytes),
+                       'net_objects_sharing_the_set': int(workers[0].dgr.inlier_model._handle().sharers),
+                       'voxels_per_pair': [int(b0['off0'][-1] / nb), int(b0['off1'][-1] / nb)],
+                       'pairs_per_step': pairs_per_step,
+                       'distinct_input_sets': (max(1, args.rotate_sets) if rotate else 1),
+                       'refinement': not args.no_refine,
+                       'use_icp': bool(args.full_register), 'forced_safeguard': bool(args.force_safeguard),
+                       'parallelism': f'pair-sharded x{world}, no data-path collective'},
+            'host_cpu_s_per_step_per_rank': cpu_s_per_step,
+            # ... of which the stream-driving threads themselves (enqueueing a batch's launches, then sleeping until it is
+            # done: dgr_ctx_wait); the rest is the HIP runtime's own threads
+            'host_cpu_s_per_step_driver_threads': sum(getattr(w, 'thread_cpu_s', 0.0) for w in workers) / args.steps,
+            # one-time start-up of a rank, MAX over ranks: the RCCL broadcast of the checkpoint (ranks > 0 receive ~0.94 GB
+            # into HBM and keep it there) and the preparation of the kernels' weight layouts (ranks > 0, and a forced
+            # one-rank group: by HIP kernels from the broadcast buffer, dgr_net_create_device; the source rank: from its host
+            # copy)
+            'startup_s': startup,
+            'te_m_mean': float(np.mean(te)) if te else None, 're_deg_mean': float(np.mean(re)) if re else None,
+            'status_counts': {str(k): int((status_all == k).sum()) for k in np.unique(status_all)},
+            'iterations_mean': float(stats_all[:, 0].mean()),
+        }
+
+    if not args.full:
+        # a plain run ends here: set-up, warm-up, the timed steps, their outputs and the result line
+        if rank == 0:
+            print(json.dumps(out))
+        if pg_up:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the same stream configuration once more, profiled: every worker at once, HIP events around every conv launch on
     #      the worker's own stream (roofline.frac is quoted from HERE: the configuration the headline was timed in)
@@ -661,7 +764,6 @@ def main():
 
     # ---- profiled re-run of stream 0's first batch alone: HIP events around every sparse-conv launch ----
     _lib.use_ctx(w0.ctx)
-    cus_timed = w0.cus        # compute units a launch of the timed configuration ran on (None: all of them)
     if w0.cus:
         # ... alone on the WHOLE GPU: the per-kernel figures (frac_one_stream, by_kernel, the C <= 64 group, stage times,
         # the PMC passes of tools/evidence.sh) are the kernels' own, not those of a quarter of the compute units
@@ -686,8 +788,7 @@ def main():
 
     if rank == 0:
         dgr = w0.dgr
-        off0, off1, C0, X0, C1, X1, idx1 = bt['off0'], bt['off1'], bt['C0'], bt['X0'], bt['C1'], bt['X1'], bt['idx1']
-        nb = len(bt['ids'])
+        C0, X0, C1, X1, idx1 = bt['C0'], bt['X0'], bt['C1'], bt['X1'], bt['idx1']
         # algorithmic work of the conv kernels per batch, from the kernel maps of this very input
         with torch.cuda.stream(w0.stream):
             fc = dgr.fcgf_model._handle()
@@ -749,17 +850,6 @@ def main():
                         'algorithmic_bytes_per_launch': sum(layer_bytes(st) for st, _ in sel) / len(sel)}
         conv_ms = prof['conv_kernels']
         achieved = flop / (conv_ms * 1e-3) / 1e12
-        T_all, status_all, stats_all = gathered
-        ids_all = [int(round(v)) for v in gathered_ids[0][:, 0, 0]]
-        if args.dump_results:
-            np.savez(args.dump_results, ids=np.asarray(ids_all), T=T_all, status=status_all, stats=stats_all)
-        te, re = [], []
-        for p, seed in enumerate(ids_all):
-            if (int(status_all[p]) & 0xff) in (0, 3):   # estimated by the network path or by the safeguard RANSAC (flags masked)
-                Tg = vox_cache[seed][2] if seed in vox_cache else synth.synth_pair(seed, n_raw=args.n_raw, kind=args.kind)[2]
-                te.append(float(np.linalg.norm(T_all[p][:3, 3] - Tg[:3, 3])))
-                c = (np.trace(T_all[p][:3, :3].T @ Tg[:3, :3]) - 1) / 2
-                re.append(float(np.degrees(np.arccos(np.clip(c, -1, 1)))))
         # HBM traffic / MFMA-busy of the dominant kernel from PMC counters: separate rocprofv3 --pmc passes on
         # the same per-stream workload (tools/evidence.sh), committed under profiles/ -- not measurable from inside
         # this process; quoted only when kernel name and workload label match this run
@@ -777,8 +867,6 @@ def main():
         products = PRODUCTS_PER_MAC if split else 1
         peak = PEAK_F16_MFMA_TFLOPS if split else PEAK_FP32_MFMA_TFLOPS
         alg = dominant['achieved_tflops'] if dominant else achieved
-        pairs_per_step = (args.total_pairs or world * n_local)
-        ms_per_step = elapsed / args.steps * 1e3
         # the dominant kernel in the TIMED stream configuration (all streams of the rank at once, HIP events on each
         # stream): the duration roofline.frac is computed from; the one-stream figure next to it
         tc = [u for k_, u in timed_cfg_launches if dominant and k_ == dominant['name'] and u > 0]
@@ -791,7 +879,6 @@ def main():
         alg_timed = gfl / (us_timed * 1e-6) / 1e3 if us_timed else alg        # TFLOP/s
         traffic = pmc.get('hbm_bytes_per_launch') if pmc else None
         alg_bytes = dominant['algorithmic_bytes_per_launch'] if dominant else byts / n_launch
-        ncu_all = torch.cuda.get_device_properties(device).multi_processor_count
         # a launch of the timed configuration runs on this share of the CUs -- when its duration there is known (the kernel
         # stamped it); otherwise `us_timed` is the one-stream, whole-GPU duration and so is the peak
         share = (cus_timed / ncu_all) if (cus_timed and tc) else 1.0
@@ -871,55 +958,16 @@ def main():
             'dominant_spans_us_timed_config': ([round(float(u), 1) for u in _group_launches(timed_cfg_launches).get(dominant['name'], [])][:96]
                                                if dominant else []),
         }
-        out = {
-            'metric': 'pair registrations/sec (FCGF x2 + 1-NN + 6-D inlier net + gate + weighted Procrustes + SE(3) refinement'
-                      + (' + ICP' if args.full_register else '') + (', safeguard RANSAC forced' if args.force_safeguard else '') + ')',
-            'value': pairs_per_step * args.steps / elapsed, 'unit': 'pairs/s', 'n_gpus': world,
-            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
-            'higher_is_better': True, 'scaling': 'strong' if args.total_pairs else 'weak', 'vs_baseline': None,
-            'dtype': ('f32 results via 2 x f16 split operands (3 f16 MFMA products per MAC, f32 accumulate); k = 1 convs, '
-                      'kNN re-evaluation and registration in exact f32, SVD in f64') if split else
-                     'f32 (v_mfma_f32_*_f32 on the f32 operands: DGR_EXACT_F32=1); SVD in f64',
-            'data': 'synthetic 3DMatch-shaped pairs, seeded synthetic weights, teacher-forced matches (20% GT) and inlier logits'
-                    + ('; PCIe-inclusive: raw host points -> H2D -> voxelisation inside the timed region' if args.from_host else ''),
-            'config': {'workload': f'{pairs_per_step} pairs/step ({world} GPU(s) x {len(workers)} stream(s) x batches of {B}), '
-                                   f'{args.n_raw} raw pts/fragment, {args.kind}, voxel {args.voxel}, conv1 k={args.conv1_ks} '
-                                   f'({cfg_label(args)})',
-                       'streams_per_gpu': len(workers),
-                       'cu_partition': (f'{len(workers)} contexts on {partition} shares of {cus_timed} of {ncu_all} compute units each '
-                                        '(CU-masked streams, dgr_ctx_create_partition_stream)') if cus_timed else 'none (plain streams)',
-                       'warmup_steps_run': workers[0].warmup_steps,
-                       # weight sets resident per GPU (the streams share one: dgr_net_share) and their bytes
-                       'weight_sets_per_gpu': (1 if workers[0].dgr.inlier_model._handle().sharers == len(workers) else len(workers)),
-                       'weight_bytes_per_set': int(workers[0].dgr.fcgf_model._handle().param_bytes
-                                                   + workers[0].dgr.inlier_model._handle().param_bytes),
-                       'net_objects_sharing_the_set': int(workers[0].dgr.inlier_model._handle().sharers),
-                       'voxels_per_pair': [int(off0[-1] / nb), int(off1[-1] / nb)],
-                       'pairs_per_step': pairs_per_step,
-                       'distinct_input_sets': (max(1, args.rotate_sets) if rotate else 1),
-                       'refinement': not args.no_refine,
-                       'use_icp': bool(args.full_register), 'forced_safeguard': bool(args.force_safeguard),
-                       'parallelism': f'pair-sharded x{world}, no data-path collective'},
+        out['dtype'] = dtype_label(split)
+        out.update({
             # roofline of the DOMINANT conv kernel variant against the pipe it issues on (scalars first: the fields a reader
             # needs to reproduce `frac` by hand; the per-kernel / per-layer records are in `roofline_detail`)
             'roofline': roofline,
             'roofline_detail': roofline_detail,
-            'host_cpu_s_per_step_per_rank': cpu_s_per_step,
-            # ... of which the stream-driving threads themselves (enqueueing a batch's launches, then sleeping until it is
-            # done: dgr_ctx_wait); the rest is the HIP runtime's own threads
-            'host_cpu_s_per_step_driver_threads': sum(getattr(w, 'thread_cpu_s', 0.0) for w in workers) / args.steps,
-            # one-time start-up of a rank, MAX over ranks: the RCCL broadcast of the checkpoint (ranks > 0 receive ~0.94 GB
-            # into HBM and keep it there) and the preparation of the kernels' weight layouts (ranks > 0, and a forced
-            # one-rank group: by HIP kernels from the broadcast buffer, dgr_net_create_device; the source rank: from its host
-            # copy)
-            'startup_s': startup,
             'stage_ms_per_batch': {k: round(v, 3) for k, v in prof.items() if k != 'conv_launches'},
-            'te_m_mean': float(np.mean(te)) if te else None, 're_deg_mean': float(np.mean(re)) if re else None,
-            'status_counts': {str(k): int((status_all == k).sum()) for k in np.unique(status_all)},
-            'iterations_mean': float(stats_all[:, 0].mean()),
             'layers_6d': [[x['pairs'], x['nonempty'], x['n_in'], x['n_out'], x['cin'], x['cout']] for x in s_c],
             'layers_3d_batch': [[x['pairs'], x['nonempty'], x['n_in'], x['n_out'], x['cin'], x['cout']] for x in s_a],
-        }
+        })
         log('roofline accounting done')
         out['parity'] = out['cpu_baseline'] = None
         if not args.no_parity and world == 1:
@@ -956,7 +1004,7 @@ def main():
         #      one short leg in a child process (the switch is read when the library first runs a layer); outside the timed region
         if world == 1 and not args.no_exact_leg and not args.no_parity and not os.environ.get('DGR_EXACT_F32'):
             try:
-                cmd = [sys.executable, os.path.abspath(__file__), '--steps', '8', '--warmup', '2', '--no-parity', '--no-exact-leg',
+                cmd = [sys.executable, os.path.abspath(__file__), '--full', '--steps', '8', '--warmup', '2', '--no-parity', '--no-exact-leg',
                        '--pairs-per-step', str(B), '--streams', str(S), '--n-raw', str(args.n_raw), '--voxel', str(args.voxel),
                        '--kind', args.kind, '--conv1-ks', str(args.conv1_ks)] + (['--no-refine'] if args.no_refine else []) \
                     + (['--no-cu-partition'] if args.no_cu_partition else []) + ['--cu-shares', str(args.cu_shares)]

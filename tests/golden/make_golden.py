@@ -224,6 +224,17 @@ def main():
                         traj_meta=np.array([t.metadata for t in traj]), traj_pose=np.stack([t.pose for t in traj]),
                         poses_written=np.stack(poses), T_pred=np.stack(Tp), T_gt=np.stack(Tg), rte_rre=np.stack(res),
                         rte_rre_none=ref_rte_rre(None, Tg[0], 0.3, 15))
+    # the two poses of tests/test_eval_cpu.py::test_rte_rre_matches_reference_definition (its `_pose` on seed 0)
+    r5 = np.random.default_rng(0)
+    AB = []
+    for _ in range(2):
+        q, _ = np.linalg.qr(r5.standard_normal((3, 3)))
+        if np.linalg.det(q) < 0:
+            q[:, 0] *= -1
+        T = np.eye(4); T[:3, :3] = q; T[:3, 3] = r5.standard_normal(3)
+        AB.append(T)
+    np.savez_compressed(os.path.join(HERE, 'rte_rre_definition.npz'), A=AB[0], B=AB[1],
+                        rte_rre=np.asarray(ref_rte_rre(AB[0], AB[1], 0.3, 15), np.float64))
     print('golden vectors written to', HERE)
 
 

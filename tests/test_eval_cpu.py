@@ -1,6 +1,4 @@
 """Evaluation harness and file formats -- host-side, CPU only."""
-import os
-
 import numpy as np
 import pytest
 
@@ -15,9 +13,8 @@ def _pose(rng):
     return T
 
 
-def test_rte_rre_matches_reference_definition():
+def test_rte_rre_matches_reference_definition(golden):
     import math
-    import sys
     rng = np.random.default_rng(0)
     A, B = _pose(rng), _pose(rng)
     s, rte, rre = ev.rte_rre(A, B, 0.3, 15)
@@ -26,15 +23,11 @@ def test_rte_rre_matches_reference_definition():
     assert s == 0
     np.testing.assert_array_equal(ev.rte_rre(None, B, 0.3, 15), [0, np.inf, np.inf])
     assert ev.rte_rre(B, B, 0.3, 15)[0] == 1 and ev.rte_rre(B, B, 0.3, 15)[2] < 1e-5
-    try:   # the reference's own function, when the reference tree is present (not on the GPU box)
-        sys.path.insert(0, '/root/reference/scripts')
-        src = open('/root/reference/scripts/test_3dmatch.py').read()
-    except OSError:
-        return
-    ns = {'np': np, 'math': math}
-    start = src.index('def rte_rre'); end = src.index('def analyze_stats')
-    exec(src[start:end], ns)
-    np.testing.assert_allclose(ev.rte_rre(A, B, 0.3, 15), ns['rte_rre'](A, B, 0.3, 15), rtol=1e-12)
+    # the reference's own function (scripts/test_3dmatch.py:38-46) on the same two poses, stored by tests/golden/make_golden.py
+    g = golden('rte_rre_definition')
+    np.testing.assert_array_equal(A, g['A'])
+    np.testing.assert_array_equal(B, g['B'])
+    np.testing.assert_allclose(ev.rte_rre(A, B, 0.3, 15), g['rte_rre'], rtol=1e-12)
 
 
 def test_trajectory_kitti_and_ply_round_trips(tmp_path):
@@ -153,17 +146,16 @@ def test_kitti_pairs_ground_truth_and_loop(tmp_path):
         ev.KITTIOdometryPairs(str(root), [7])
 
 
-def test_trajectory_reader_and_rte_rre_match_the_reference(golden):
+def test_trajectory_reader_and_rte_rre_match_the_reference(golden, tmp_path):
     """`read_trajectory` (util/file.py:69-90) and `rte_rre` (scripts/test_3dmatch.py:38-46): the reference's own
     functions were run on a generated gt.log / pose set by tests/golden/make_golden.py; the product's reader and
     metric must reproduce their outputs on the same inputs."""
     from deepglobalregistration_amd.eval import formats, metrics
     g = golden('eval_formats')
-    path = os.path.join(os.environ.get('TMPDIR', '/tmp'), 'dgr_gt_golden.log')
+    path = str(tmp_path / 'gt_golden.log')
     with open(path, 'w') as f:
         f.write(str(g['gt_log_text']))
     traj = formats.read_trajectory(path)
-    os.unlink(path)
     assert len(traj) == len(g['traj_meta'])
     for rec, meta, pose in zip(traj, g['traj_meta'], g['traj_pose']):
         m, T = (rec.metadata, rec.pose) if hasattr(rec, 'pose') else rec

@@ -31,7 +31,8 @@ def _bench(tmp, gpus, tag='', **extra_env):
     for k in [k for k, v in env.items() if v is None]:
         env.pop(k)
     out = os.path.join(tmp, f'res{gpus}{tag}.npz')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--dump-results', out, *COMMON],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--dump-results', out,
+                        '--dump-outputs', os.path.join(tmp, f'outputs{gpus}{tag}'), *COMMON],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
@@ -39,9 +40,32 @@ def _bench(tmp, gpus, tag='', **extra_env):
 
 
 @pytest.fixture(scope='module')
-def plain_run(tmp_path_factory):
+def plain_dir(tmp_path_factory):
+    return str(tmp_path_factory.mktemp('plain'))
+
+
+@pytest.fixture(scope='module')
+def plain_run(plain_dir):
     """The plain one-rank run (no process group) both tests compare with."""
-    return _bench(str(tmp_path_factory.mktemp('plain')), 1)
+    return _bench(plain_dir, 1)
+
+
+def test_dump_outputs_hold_the_last_timed_step(plain_dir, plain_run):
+    """`--dump-outputs DIR`: what the timed path returned in its last step, float64, ordered by pair id -- the same values
+    as `--dump-results`; a plain run's line carries the headline fields and none of what `--full` measures."""
+    line, r1, _ = plain_run
+    d = os.path.join(plain_dir, 'outputs1')
+    o = np.argsort(r1['ids'])
+    got = {k: np.load(os.path.join(d, k + '.npy')) for k in ('pair_ids', 'T', 'status', 'stats')}
+    assert all(a.dtype == np.float64 for a in got.values())
+    np.testing.assert_array_equal(got['pair_ids'], np.arange(6))
+    np.testing.assert_array_equal(got['T'], r1['T'][o])
+    np.testing.assert_array_equal(got['status'], r1['status'][o])
+    np.testing.assert_array_equal(got['stats'], r1['stats'][o].astype(np.float64))
+    assert line['steps'] == 2 and line['ms_per_step'] > 0 and line['unit'] == 'pairs/s' and line['higher_is_better']
+    assert line['value'] == pytest.approx(6 * 1e3 / line['ms_per_step'], rel=1e-9)
+    assert ('split operands' in line['dtype']) == ('DGR_EXACT_F32' not in os.environ)
+    assert not {'roofline', 'parity', 'cpu_baseline', 'exact_f32_leg'} & set(line)
 
 
 def test_two_ranks_cover_every_pair_once_and_match_one_rank(tmp_path, plain_run):

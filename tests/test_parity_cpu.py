@@ -47,7 +47,7 @@ def test_a_reordered_implementation_stays_inside_the_reported_band():
 
 
 def test_bench_checker_legs_run_on_cpu(monkeypatch):
-    """`bench.py`'s parity + CPU-baseline leg (the part of the driver's no-flag command that runs AFTER the timed
+    """`bench.py`'s parity + CPU-baseline leg (the part `bench.py --full` runs AFTER the timed
     region) end to end on a tiny pair, with the oracle itself standing in for the HIP outputs and the HIP refinement:
     every key the bench line promises is there, the deviations are rounding noise, the flags say so.  (Round 4 shipped a name
     collision in this function to the GPU box once: nothing on the CPU side executed it.)"""

@@ -4,7 +4,7 @@
 R=$PWD; tag=$1; shift; O=$R/gpurun_out/ab_$tag; mkdir -p $O
 for lib in "$@"; do
   n=$(basename $(dirname $lib))
-  DGR_HIP_LIB=$R/$lib timeout 300 python $R/bench.py --streams 1 --pairs-per-step 4 --no-parity --steps 10 --warmup 2 > $O/bench_$n.json 2> $O/bench_$n.err
+  DGR_HIP_LIB=$R/$lib timeout 300 python $R/bench.py --full --streams 1 --pairs-per-step 4 --no-parity --steps 10 --warmup 2 > $O/bench_$n.json 2> $O/bench_$n.err
   DGR_HIP_LIB=$R/$lib timeout 300 python $R/tests/aux/net_modes_dump.py $O/dump_$n.npz > $O/dump_$n.log 2>&1
   python - <<PY
 import json

@@ -6,7 +6,7 @@
 # (nopmc: everything but the counter passes -- for a refresh after changes that did not touch the profiled kernels)
 R=$PWD; O=$R/gpurun_out/final; mkdir -p $O; rm -rf $O/*
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py"
+B="python $R/bench.py --full"   # every line of the bundle carries the roofline / parity / baseline fields
 RND=r06
 W="BASELINE configs[1], 6 pairs per batch"
 # the commit these files belong to: written into tools/COMMIT by the caller before gpurun snapshots the tree (the box has
@@ -41,7 +41,7 @@ P
   rm -rf $O/pmc
   cp $O/dominant_pmc.json $R/profiles/${RND}_dominant_pmc.json    # the lines below quote it (roofline.traffic)
 fi
-# the driver's command: no flags (4 contexts x 6 pairs, each context on its own quarter of the compute units; 5 warm-up + 100
+# the driver's command with --full: no other flags (4 contexts x 6 pairs, each context on its own quarter of the compute units; 5 warm-up + 100
 # timed steps, two input sets taken in turn, parity + CPU baseline)
 timeout 900 $B > $O/bench_c1_default.json 2> $O/bench_c1_default.err
 # the default of rounds 5-6 until the CU partition: three plain streams x 6 pairs competing for all compute units; and 3 x 4 (rounds 1-4)

@@ -24,7 +24,7 @@ def main():
                 dur.append(avg)
     per = {k: c[k] / max(1, disp[k]) for k in c}
     out = {'kernel': pat, 'workload': workload, 'dispatches_per_pass': disp,
-           'command': 'rocprofv3 --kernel-trace --pmc <set> -- python bench.py --streams 1 --steps 2 --warmup 1 --no-parity '
+           'command': 'rocprofv3 --kernel-trace --pmc <set> -- python bench.py --full --streams 1 --steps 2 --warmup 1 --no-parity '
                       '[--pairs-per-step as the workload label says] (one pass per counter set, tools/evidence.sh)',
            'per_dispatch': per, 'avg_duration_us_profiled': sum(dur) / max(1, len(dur)) / 1e3}
     if 'FETCH_SIZE' in per and 'WRITE_SIZE' in per:

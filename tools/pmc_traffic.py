@@ -31,7 +31,7 @@ def main():
         if any(k in name for k in LAYER_KERNELS) and 'conv1_probe' not in name:
             launches += max(n, n2)
     out = {'command': 'rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --kernel-include-regex '
-                      '"sparse_conv|reduce_rows|conv_small|conv1_" -- python bench.py --streams 1 --pairs-per-step 4 '
+                      '"sparse_conv|reduce_rows|conv_small|conv1_" -- python bench.py --full --streams 1 --pairs-per-step 4 '
                       '--steps 2 --warmup 1 --no-cpu-baseline (two separate passes)',
            'note': 'fetch_bytes_corrected = 2 x FETCH_SIZE x 1024 (gfx950 correction); WRITE_SIZE x 1024 as is',
            'kernels': kernels, 'conv_launches': launches,
