@@ -407,9 +407,8 @@ int dgr_conv_os_launch(const DgrConvOsLaunch &a, hipStream_t stream, const char 
   DGR_REQUIRE(a.n_in_cap > 0 && a.n_in_cap * (int64_t)a.in_ld < (1ll << 32) / 4 * 4,
               "output-stationary conv: input tensor beyond 32-bit element offsets");
   ConvOsArgs ka;
-  static const bool os_f32 = getenv("DGR_EXACT_F32") != nullptr;
   ka.in = a.in; ka.out = a.out; ka.w16 = a.w16; ka.shift = a.shift; ka.res = a.res;
-  ka.wb3 = os_f32 ? nullptr : static_cast<const uint4 *>(a.wb3);
+  ka.wb3 = dgr_exact_f32() ? nullptr : static_cast<const uint4 *>(a.wb3);
   ka.piece_stride = a.piece_stride;
   ka.row_amax = ka.wb3 ? a.row_amax : nullptr;
   ka.w_unscale = a.w_unscale;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -38,6 +39,14 @@ void dgr_set_error(const char *fmt, ...);
   } while (0)
 
 #define DGR_LAUNCH_CHECK() DGR_HIP_CHECK(hipGetLastError())
+
+// DGR_EXACT_F32=1: every conv on v_mfma_f32_*_f32 with the f32 operands themselves (the reference's arithmetic,
+// conv.hip / conv_os.hip) -- the mode the split-operand kernels are measured against.  Default: two f16 pieces per
+// operand under power-of-two scales, three products per MAC (conv_wide.hip, conv_os.hip).  Read once per process.
+inline bool dgr_exact_f32() {
+  static const bool on = getenv("DGR_EXACT_F32") != nullptr;
+  return on;
+}
 
 // ------------------------------------------------------------------------------------------
 // grow-only device arena (reset at the start of every top-level call)

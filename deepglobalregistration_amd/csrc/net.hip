@@ -4,7 +4,7 @@
 // model/residual_block.py:83-134, eval batch norm model/common.py:11-21.
 //
 // Load time: eval-mode batch norm is folded into the kernels (scale) and a per-channel shift; the
-// kernels are re-tiled into the MFMA B-operand order documented in conv.hip.
+// kernels are re-tiled on the device into the MFMA B-operand order documented in conv.hip.
 // Forward: every conv is one of the kernel families of conv.hip / conv_os.hip / conv_wide.hip (chosen per layer in
 // Fwd::conv); rule-major layers write per-pair product rows that a deterministic reduction sums on top of the folded
 // shift (+ residual).  ReLU is never a separate pass: a tensor carries a "ReLU pending" flag and the consumer applies
@@ -28,18 +28,18 @@ static constexpr float BN_EPS = 1e-5f;
 struct DgrLayer {
   std::string name;
   int K, cin, cout, cin_pad, cout_pad;
-  float *w = nullptr;      // device, tiled
-  float *w16 = nullptr;    // device, 16x16x4 fragment order (3-D K = 27 layers: output-stationary conv, conv_os.hip)
-  void *w16b = nullptr;    // device, the same as two f16 pieces in 16x16x32 fragment order (conv_os.hip)
-  void *w16d = nullptr;    // device, the pieces once more in the channel order of the dense-tile kernel's gather (conv_dense.hip)
+  // device operand layouts: views into DgrWeights::allocs (which owns them)
+  float *w = nullptr;      // tiled
+  float *w16 = nullptr;    // 16x16x4 fragment order (3-D K = 27 layers: output-stationary conv, conv_os.hip)
+  void *w16b = nullptr;    // the same as two f16 pieces in 16x16x32 fragment order (conv_os.hip)
+  void *w16d = nullptr;    // the pieces once more in the channel order of the dense-tile kernel's gather (conv_dense.hip)
   int64_t w16b_piece = 0;
-  float *wc = nullptr;     // device, conv1 weights in the operand order of conv1_grid_mfma (3-D conv1 with one input channel)
-  float *wq = nullptr;     // device, conv1 weights quad-major for conv_cin6_quad_kernel (6-D conv1 with six input channels)
-  void *wb = nullptr;      // device, two f16 pieces in 32x32x16 fragment order (wide layers, conv_wide.hip)
+  float *wc = nullptr;     // conv1 weights in the operand order of conv1_grid_mfma (3-D conv1 with one input channel)
+  float *wq = nullptr;     // conv1 weights quad-major for conv_cin6_quad_kernel (6-D conv1 with six input channels)
+  void *wb = nullptr;      // two f16 pieces in 32x32x16 fragment order (wide layers, conv_wide.hip)
   int64_t wb_piece = 0;    // 16-byte units per piece
-  int pieces = 2;          // wb / w16b: two f16 pieces of 2^e W; w_unscale = 2^-e
-  float w_unscale = 1.f;
-  float *shift = nullptr;  // device [cout] or nullptr
+  float w_unscale = 1.f;   // wb / w16b hold the two f16 pieces of 2^e W; w_unscale = 2^-e
+  float *shift = nullptr;  // [cout] or nullptr
 };
 
 struct LayerRun {  // bookkeeping of the last forward, for dgr_net_layer_stats / dgr_net_rerun_layer
@@ -74,8 +74,14 @@ struct DgrTensorRef {
 // from it with dgr_net_share -- one context per HIP stream, ONE weight set per device.
 struct DgrWeights {
   std::vector<DgrLayer> layers;  // 23 convs in forward order
+  std::vector<void *> allocs;    // every device buffer the layers point into, recorded as soon as it is allocated
   int64_t param_bytes = 0;
   int device = 0;
+  template <class T> int alloc(T **p, size_t n) {
+    DGR_HIP_CHECK(hipMalloc((void **)p, n * sizeof(T)));
+    allocs.push_back(*p);
+    return DGR_OK;
+  }
   // Runs on whichever host thread drops the last reference (e.g. Python's GC inside a worker thread): the thread's current
   // device is restored afterwards; the synchronisation stalls every stream of THIS device once, when the last sharer goes.
   ~DgrWeights() {
@@ -83,16 +89,7 @@ struct DgrWeights {
     (void)hipGetDevice(&cur);
     (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();
-    for (auto &l : layers) {
-      if (l.w) (void)hipFree(l.w);
-      if (l.w16) (void)hipFree(l.w16);
-      if (l.wb) (void)hipFree(l.wb);
-      if (l.wc) (void)hipFree(l.wc);
-      if (l.wq) (void)hipFree(l.wq);
-      if (l.w16b) (void)hipFree(l.w16b);
-      if (l.w16d) (void)hipFree(l.w16d);
-      if (l.shift) (void)hipFree(l.shift);
-    }
+    for (void *p : allocs) (void)hipFree(p);
     if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
   }
 };
@@ -115,20 +112,18 @@ static const dgr_weight_desc *find_desc(const dgr_weight_desc *w, int n, const s
   return nullptr;
 }
 
-// ---- the same re-tilings ON THE DEVICE (dgr_net_create_device: the checkpoint's tensors are already in HBM, e.g. out of
-// the RCCL broadcast buffer of a multi-GPU start -- no copy back to the host, no host-side loops over 236 M parameters).
-// Every kernel below computes element o of a destination layout exactly as the host loops of make_layer do (same index
-// arithmetic, the same left-to-right f32 products, the same f16 roundings): the two paths give bit-identical weight sets
-// (tests/test_gpu_device_weights.py).
+// ---- weight preparation: HIP kernels turn the [K, cin, cout] kernel tensor in HBM (the caller's with
+// dgr_net_create_device, uploaded by dgr_net_create) into every operand layout the conv kernels read, one elementwise
+// kernel per layout; only the per-channel batch-norm vectors (cout floats each) are folded on the host.
 template <class F>
 __global__ void __launch_bounds__(256) dgr_fill_kernel(int64_t n, F f) {
   for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < n; o += (int64_t)gridDim.x * 256) f(o);
 }
 template <class F>
-static int dgr_fill(int64_t n, F f) {
+static int dgr_fill(hipStream_t s, int64_t n, F f) {
   if (n <= 0) return DGR_OK;
   const int64_t blocks = std::min<int64_t>((n + 255) / 256, 1 << 16);
-  dgr_fill_kernel<<<(int)blocks, 256>>>(n, f);
+  dgr_fill_kernel<<<(int)blocks, 256, 0, s>>>(n, f);
   DGR_LAUNCH_CHECK();
   return DGR_OK;
 }
@@ -146,159 +141,24 @@ __global__ void __launch_bounds__(256) dgr_absmax_scaled_kernel(const float *__r
   if ((threadIdx.x & 63) == 0) atomicMax(out_bits, __float_as_uint(mx));   // non-negative floats order like their bits
 }
 
-// make_layer's second half for a kernel tensor that is ALREADY in HBM (src = [K, cin, cout] f32, device): every layout the
-// conv kernels read, produced by the fill kernels above; scale / shift = the folded batch norm (host, cout floats).
-static int make_layer_device(dgr_net *net, DgrLayer L, const float *src, const std::vector<float> &scale,
-                             const std::vector<float> &shift, bool has_shift, const std::string &name) {
-  const int K = L.K, cin = L.cin, cout = L.cout;
-  static const bool exact_f32 = getenv("DGR_EXACT_F32") != nullptr;
-  L.pieces = 2;
-  float *sc = nullptr;       // scale[] on the device
-  uint32_t *mxb = nullptr;
-  DGR_HIP_CHECK(hipMalloc((void **)&sc, (size_t)cout * sizeof(float)));
-  DGR_HIP_CHECK(hipMemcpy(sc, scale.data(), (size_t)cout * sizeof(float), hipMemcpyHostToDevice));
-  DGR_HIP_CHECK(hipMalloc((void **)&mxb, sizeof(uint32_t)));
-  DGR_HIP_CHECK(hipMemset(mxb, 0, sizeof(uint32_t)));
-  struct Tmp {   // freed on every exit (after the fill kernels have run: hipFree synchronises)
-    float *a; uint32_t *b;
-    ~Tmp() { (void)hipFree(a); (void)hipFree(b); }
-  } tmp{sc, mxb};
-  float w_scale = 1.f;
-  {
-    const int64_t n = (int64_t)K * cin * cout;
-    dgr_absmax_scaled_kernel<<<(int)std::min<int64_t>((n + 255) / 256, 4096), 256>>>(src, sc, n, cout, mxb);
-    DGR_LAUNCH_CHECK();
-    uint32_t bits = 0;
-    DGR_HIP_CHECK(hipMemcpy(&bits, mxb, sizeof(bits), hipMemcpyDeviceToHost));
-    float mx;
-    memcpy(&mx, &bits, 4);
-    int e = 0;
-    if (mx > 0.f && std::isfinite(mx)) (void)frexpf(mx, &e);
-    e = std::min(std::max(e, -100), 100);
-    w_scale = ldexpf(1.f, 15 - e);
-    L.w_unscale = ldexpf(1.f, e - 15);
+// One net_create's preparation state: a private stream (default flags: ordered after the caller's NULL-stream work) and
+// device temporaries that every layer reuses in stream order; released on every exit.
+struct WeightPrep {
+  bool dev;                    // the descriptors hold device pointers (dgr_net_create_device)
+  hipStream_t s = nullptr;
+  float *sc = nullptr;         // the layer's scale[] (cout <= 256)
+  uint32_t *mxb = nullptr;     // the layer's largest |w| (bits)
+  float *staging = nullptr;    // dgr_net_create: the layer's kernel tensor, uploaded (staging_n floats)
+  size_t staging_n = 0;
+  ~WeightPrep() {
+    if (s) (void)hipStreamSynchronize(s);
+    (void)hipFree(sc); (void)hipFree(mxb); (void)hipFree(staging);
+    if (s) (void)hipStreamDestroy(s);
   }
-  const bool use_wide = K > 1 && !exact_f32 && dgr_conv_wide_supported(L.cin_pad, cin, cout) && !(net->D == 3 && K == 27);
-  if (use_wide) {
-    const int S16 = cin / 16, NB32 = cout / 32;
-    L.wb_piece = (int64_t)K * S16 * NB32 * 64;
-    const int64_t ne = L.wb_piece * 8;
-    uint16_t *dst;
-    DGR_HIP_CHECK(hipMalloc((void **)&dst, (size_t)2 * ne * sizeof(uint16_t)));
-    L.wb = dst;
-    DGR_CHECK(dgr_fill(ne, [=] __device__(int64_t o) {
-      const int e = (int)(o & 7), lane = (int)((o >> 3) & 63);
-      const int64_t r = o >> 9;
-      const int nb = (int)(r % NB32), s2 = (int)((r / NB32) % S16), k = (int)(r / ((int64_t)NB32 * S16));
-      const int col = 32 * nb + (lane & 31), row = 16 * s2 + 8 * (lane >> 5) + e;
-      const float xs = __fmul_rn(__fmul_rn(src[((size_t)k * cin + row) * cout + col], sc[col]), w_scale);
-      dst[o] = dgr_f16_bits_dev(xs);
-      dst[ne + o] = dgr_f16_bits_dev(xs - dgr_f16_val_dev(xs));
-    }));
-    net->W->param_bytes += (size_t)2 * ne * sizeof(uint16_t);
-  } else {
-    const int S = L.cin_pad / 8, NBLK = L.cout_pad / 32;
-    const int64_t ne = (int64_t)K * S * NBLK * 256;
-    float *dst;
-    DGR_HIP_CHECK(hipMalloc((void **)&dst, (size_t)ne * sizeof(float)));
-    L.w = dst;
-    DGR_CHECK(dgr_fill(ne, [=] __device__(int64_t o) {
-      const int c = (int)(o & 3), lane = (int)((o >> 2) & 63);
-      const int64_t r = o >> 8;
-      const int nb = (int)(r % NBLK), s2 = (int)((r / NBLK) % S), k = (int)(r / ((int64_t)NBLK * S));
-      const int row = 8 * s2 + 4 * (lane >> 5) + c, col = 32 * nb + (lane & 31);
-      dst[o] = (row < cin && col < cout) ? __fmul_rn(src[((size_t)k * cin + row) * cout + col], sc[col]) : 0.f;
-    }));
-    net->W->param_bytes += (size_t)ne * sizeof(float);
-  }
-  if (net->D == 3 && K == 27 && L.cin_pad % 16 == 0 && cout % 32 == 0) {
-    const int GT = L.cin_pad / 16, NB = cout / 16;
-    {
-      const int64_t ne = (int64_t)K * GT * NB * 256;
-      float *dst;
-      DGR_HIP_CHECK(hipMalloc((void **)&dst, (size_t)ne * sizeof(float)));
-      L.w16 = dst;
-      DGR_CHECK(dgr_fill(ne, [=] __device__(int64_t o) {
-        const int c = (int)(o & 3), lane = (int)((o >> 2) & 63);
-        const int64_t r = o >> 8;
-        const int jb = (int)(r % NB), g = (int)((r / NB) % GT), k = (int)(r / ((int64_t)NB * GT));
-        const int col = 16 * jb + (lane & 15), row = 16 * g + 4 * (lane >> 4) + c;
-        dst[o] = row < cin ? __fmul_rn(src[((size_t)k * cin + row) * cout + col], sc[col]) : 0.f;
-      }));
-      net->W->param_bytes += (size_t)ne * sizeof(float);
-    }
-    if (cin % 32 == 0) {
-      const int S32 = cin / 32;
-      L.w16b_piece = (int64_t)K * S32 * NB * 64;
-      const int64_t ne = L.w16b_piece * 8;
-      uint16_t *pcs;
-      DGR_HIP_CHECK(hipMalloc((void **)&pcs, (size_t)2 * ne * sizeof(uint16_t)));
-      L.w16b = pcs;
-      DGR_CHECK(dgr_fill(ne, [=] __device__(int64_t o) {
-        const int e = (int)(o & 7), lane = (int)((o >> 3) & 63);
-        const int64_t r = o >> 9;
-        const int jb = (int)(r % NB), sI = (int)((r / NB) % S32), k = (int)(r / ((int64_t)NB * S32));
-        const int col = 16 * jb + (lane & 15), row = 32 * sI + 8 * (lane >> 4) + e;
-        const float xs = __fmul_rn(__fmul_rn(src[((size_t)k * cin + row) * cout + col], sc[col]), w_scale);
-        pcs[o] = dgr_f16_bits_dev(xs);
-        pcs[ne + o] = dgr_f16_bits_dev(xs - dgr_f16_val_dev(xs));
-      }));
-      net->W->param_bytes += (size_t)2 * ne * sizeof(uint16_t);
-      if (net->D == 3 && K == 27 && (dgr_conv_dense_supported(cin, L.cin_pad, cout) || dgr_conv_up_supported(cin, L.cin_pad, cout))) {
-        uint16_t *pd;
-        DGR_HIP_CHECK(hipMalloc((void **)&pd, (size_t)2 * ne * sizeof(uint16_t)));
-        L.w16d = pd;
-        DGR_CHECK(dgr_fill(2 * ne, [=] __device__(int64_t o) {   // (fragments of both pieces alike)
-          const int e = (int)(o & 3), h = (int)((o >> 2) & 1);
-          const int64_t f = o >> 3, base = f & ~(int64_t)63;
-          const int lane = (int)(f & 63), col = lane & 15, lq = lane >> 4;
-          const int64_t srcf = base + col + 16 * ((lq >> 1) + 2 * h);
-          pd[o] = pcs[srcf * 8 + 4 * (lq & 1) + e];
-        }));
-        net->W->param_bytes += (size_t)2 * ne * sizeof(uint16_t);
-      }
-    }
-  }
-  if (net->D == 3 && name == "conv1" && cin == 1 && cout == 32 && K <= 343) {
-    int ks = 1;
-    while (ks * ks * ks < K) ++ks;
-    const int ks2 = ks * ks, steps = (ks2 + 3) / 4;
-    const int64_t ne = (int64_t)ks * steps * 128;
-    float *dst;
-    DGR_HIP_CHECK(hipMalloc((void **)&dst, (size_t)ne * sizeof(float)));
-    L.wc = dst;
-    DGR_CHECK(dgr_fill(ne, [=] __device__(int64_t o) {
-      const int j = (int)(o & 1), lane = (int)((o >> 1) & 63);
-      const int64_t r = o >> 7;
-      const int s2 = (int)(r % steps), kz = (int)(r / steps);
-      const int kk = 4 * s2 + (lane >> 4), col = (lane & 15) + 16 * j;
-      dst[o] = kk < ks2 ? __fmul_rn(src[(size_t)(kz * ks2 + kk) * cout + col], sc[col]) : 0.f;
-    }));
-  }
-  if (name == "conv1" && cin == 6 && cout == 32 && K > 1) {
-    const int64_t ne = (int64_t)K * 192;
-    float *dst;
-    DGR_HIP_CHECK(hipMalloc((void **)&dst, (size_t)ne * sizeof(float)));
-    L.wq = dst;
-    DGR_CHECK(dgr_fill(ne, [=] __device__(int64_t o) {
-      const int e = (int)(o & 3), q = (int)((o >> 2) & 3);
-      const int i = (int)((o >> 4) % 12), k = (int)(o / 192);
-      const int ci = i >> 1, co = 8 * q + 4 * (i & 1) + e;
-      dst[o] = __fmul_rn(src[((size_t)k * cin + ci) * cout + co], sc[co]);
-    }));
-    net->W->param_bytes += (size_t)ne * sizeof(float);
-  }
-  if (has_shift) {
-    DGR_HIP_CHECK(hipMalloc((void **)&L.shift, cout * sizeof(float)));
-    DGR_HIP_CHECK(hipMemcpy(L.shift, shift.data(), cout * sizeof(float), hipMemcpyHostToDevice));
-  }
-  DGR_HIP_CHECK(hipDeviceSynchronize());   // the fills read sc / the caller's tensors: done before either can go away
-  net->W->layers.push_back(L);
-  return DGR_OK;
-}
+};
 
-static int make_layer(dgr_net *net, const dgr_weight_desc *descs, int nd, const std::string &name, int K,
-                      int cin, int cout, const char *bn, bool bias, bool dev = false) {
+static int make_layer(dgr_net *net, WeightPrep &P, const dgr_weight_desc *descs, int nd, const std::string &name, int K,
+                      int cin, int cout, const char *bn, bool bias) {
   DgrLayer L;
   L.name = name;
   L.K = K; L.cin = cin; L.cout = cout;
@@ -320,7 +180,7 @@ static int make_layer(dgr_net *net, const dgr_weight_desc *descs, int nd, const 
   // the per-channel tensors (batch norm, bias: cout floats each) are folded on the host either way; `dev`: fetched first
   std::vector<std::vector<float>> small;
   auto host_of = [&](const dgr_weight_desc *d) -> const float * {
-    if (!dev) return d->data;
+    if (!P.dev) return d->data;
     small.emplace_back((size_t)d->numel);
     if (hipMemcpy(small.back().data(), d->data, (size_t)d->numel * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
     return small.back().data();
@@ -350,130 +210,123 @@ static int make_layer(dgr_net *net, const dgr_weight_desc *descs, int nd, const 
     for (int c = 0; c < cout; ++c) shift[c] += bh[c];
     has_shift = true;
   }
-  if (dev) return make_layer_device(net, L, kd->data, scale, shift, has_shift, name);
-  // DGR_EXACT_F32=1: every conv on v_mfma_f32_*_f32 with the f32 operands themselves (the reference's arithmetic,
-  // conv.hip / conv_os.hip) -- the mode the split-operand kernels are measured against.  Default: two f16 pieces per
-  // operand under power-of-two scales, three products per MAC (conv_wide.hip, conv_os.hip).
-  static const bool exact_f32 = getenv("DGR_EXACT_F32") != nullptr;
-  L.pieces = 2;
-  // the layer's weight scale: the largest |w| (batch norm folded in) lands in [2^14, 2^15)
-  float w_scale = 1.f;
-  {
-    float mx = 0.f;
-    for (int k = 0; k < K; ++k)
-      for (int r = 0; r < cin; ++r)
-        for (int c = 0; c < cout; ++c) mx = std::max(mx, fabsf(kd->data[((size_t)k * cin + r) * cout + c] * scale[c]));
-    int e = 0;
-    if (mx > 0.f && std::isfinite(mx)) (void)frexpf(mx, &e);   // mx in [2^(e-1), 2^e)
-    e = std::min(std::max(e, -100), 100);
-    w_scale = ldexpf(1.f, 15 - e);
-    L.w_unscale = ldexpf(1.f, e - 15);
+  DgrWeights &W = *net->W;
+  hipStream_t s = P.s;
+  const float *src = kd->data;   // [K, cin, cout] f32 on the device
+  if (!P.dev) {
+    const size_t n = (size_t)kd->numel;
+    if (n > P.staging_n) {   // grown once the earlier layers' fills are done with it
+      DGR_HIP_CHECK(hipStreamSynchronize(s));
+      DGR_HIP_CHECK(hipFree(P.staging));
+      P.staging = nullptr;
+      DGR_HIP_CHECK(hipMalloc((void **)&P.staging, n * sizeof(float)));
+      P.staging_n = n;
+    }
+    DGR_HIP_CHECK(hipMemcpyAsync(P.staging, kd->data, n * sizeof(float), hipMemcpyHostToDevice, s));
+    src = P.staging;
   }
-  auto f16_bits = [](float x) { _Float16 h = (_Float16)x; uint16_t b; memcpy(&b, &h, 2); return b; };
-  auto f16_val = [](float x) { return (float)(_Float16)x; };
-  const bool use_wide = K > 1 && !exact_f32 && dgr_conv_wide_supported(L.cin_pad, cin, cout) && !(net->D == 3 && K == 27);
+  const float *sc = P.sc;
+  DGR_HIP_CHECK(hipMemcpyAsync(P.sc, scale.data(), (size_t)cout * sizeof(float), hipMemcpyHostToDevice, s));
+  if (has_shift) {
+    DGR_CHECK(W.alloc(&L.shift, cout));
+    DGR_HIP_CHECK(hipMemcpyAsync(L.shift, shift.data(), (size_t)cout * sizeof(float), hipMemcpyHostToDevice, s));
+  }
+  // the layer's weight scale: the largest |w| (batch norm folded in) lands in [2^14, 2^15)
+  const int64_t nw = (int64_t)K * cin * cout;
+  DGR_HIP_CHECK(hipMemsetAsync(P.mxb, 0, sizeof(uint32_t), s));
+  dgr_absmax_scaled_kernel<<<(int)std::min<int64_t>((nw + 255) / 256, 4096), 256, 0, s>>>(src, sc, nw, cout, P.mxb);
+  DGR_LAUNCH_CHECK();
+  uint32_t bits = 0;
+  DGR_HIP_CHECK(hipMemcpyAsync(&bits, P.mxb, sizeof(bits), hipMemcpyDeviceToHost, s));
+  DGR_HIP_CHECK(hipStreamSynchronize(s));   // w_scale is a kernel argument below (and the host vectors are consumed)
+  float mx;
+  memcpy(&mx, &bits, 4);
+  int ex = 0;
+  if (mx > 0.f && std::isfinite(mx)) (void)frexpf(mx, &ex);   // mx in [2^(ex-1), 2^ex)
+  ex = std::min(std::max(ex, -100), 100);
+  const float w_scale = ldexpf(1.f, 15 - ex);
+  L.w_unscale = ldexpf(1.f, ex - 15);
+  const bool use_wide = K > 1 && !dgr_exact_f32() && dgr_conv_wide_supported(L.cin_pad, cin, cout) && !(net->D == 3 && K == 27);
   if (use_wide) {
     const int S16 = cin / 16, NB32 = cout / 32;
     L.wb_piece = (int64_t)K * S16 * NB32 * 64;
-    std::vector<uint16_t> pieces((size_t)2 * L.wb_piece * 8);
-    for (int k = 0; k < K; ++k) {
-      const float *src = kd->data + (size_t)k * cin * cout;
-      for (int s = 0; s < S16; ++s)
-        for (int nb = 0; nb < NB32; ++nb)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int col = 32 * nb + (lane & 31);
-            const size_t o = ((((size_t)k * S16 + s) * NB32 + nb) * 64 + lane) * 8;
-            for (int e = 0; e < 8; ++e) {
-              const float xs = src[(size_t)(16 * s + 8 * (lane >> 5) + e) * cout + col] * scale[col] * w_scale;
-              pieces[o + e] = f16_bits(xs);
-              pieces[(size_t)L.wb_piece * 8 + o + e] = f16_bits(xs - f16_val(xs));
-            }
-          }
-    }
-    DGR_HIP_CHECK(hipMalloc(&L.wb, pieces.size() * sizeof(uint16_t)));
-    DGR_HIP_CHECK(hipMemcpy(L.wb, pieces.data(), pieces.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    net->W->param_bytes += pieces.size() * sizeof(uint16_t);
+    const int64_t ne = L.wb_piece * 8;
+    uint16_t *dst;
+    DGR_CHECK(W.alloc(&dst, (size_t)2 * ne));
+    L.wb = dst;
+    DGR_CHECK(dgr_fill(s, ne, [=] __device__(int64_t o) {
+      const int e = (int)(o & 7), lane = (int)((o >> 3) & 63);
+      const int64_t r = o >> 9;
+      const int nb = (int)(r % NB32), s2 = (int)((r / NB32) % S16), k = (int)(r / ((int64_t)NB32 * S16));
+      const int col = 32 * nb + (lane & 31), row = 16 * s2 + 8 * (lane >> 5) + e;
+      const float xs = __fmul_rn(__fmul_rn(src[((size_t)k * cin + row) * cout + col], sc[col]), w_scale);
+      dst[o] = dgr_f16_bits_dev(xs);
+      dst[ne + o] = dgr_f16_bits_dev(xs - dgr_f16_val_dev(xs));
+    }));
+    W.param_bytes += (size_t)2 * ne * sizeof(uint16_t);
   } else {
-  const int S = L.cin_pad / 8, NBLK = L.cout_pad / 32;
-  const size_t per_k = (size_t)S * NBLK * 256;
-  std::vector<float> tiled((size_t)K * per_k);
-  for (int k = 0; k < K; ++k) {
-    const float *src = kd->data + (size_t)k * cin * cout;
-    float *dst = tiled.data() + (size_t)k * per_k;
-    for (int s = 0; s < S; ++s)
-      for (int nb = 0; nb < NBLK; ++nb)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int col = 32 * nb + (lane & 31);
-          float *d = dst + ((size_t)(s * NBLK + nb) * 64 + lane) * 4;
-          for (int c = 0; c < 4; ++c) {
-            const int row = 8 * s + 4 * (lane >> 5) + c;
-            d[c] = (row < cin && col < cout) ? src[(size_t)row * cout + col] * scale[col] : 0.f;
-          }
-        }
-  }
-  DGR_HIP_CHECK(hipMalloc((void **)&L.w, tiled.size() * sizeof(float)));
-  DGR_HIP_CHECK(hipMemcpy(L.w, tiled.data(), tiled.size() * sizeof(float), hipMemcpyHostToDevice));
-  net->W->param_bytes += tiled.size() * sizeof(float);
+    const int S = L.cin_pad / 8, NBLK = L.cout_pad / 32;
+    const int64_t ne = (int64_t)K * S * NBLK * 256;
+    DGR_CHECK(W.alloc(&L.w, ne));
+    float *const dst = L.w;
+    DGR_CHECK(dgr_fill(s, ne, [=] __device__(int64_t o) {
+      const int c = (int)(o & 3), lane = (int)((o >> 2) & 63);
+      const int64_t r = o >> 8;
+      const int nb = (int)(r % NBLK), s2 = (int)((r / NBLK) % S), k = (int)(r / ((int64_t)NBLK * S));
+      const int row = 8 * s2 + 4 * (lane >> 5) + c, col = 32 * nb + (lane & 31);
+      dst[o] = (row < cin && col < cout) ? __fmul_rn(src[((size_t)k * cin + row) * cout + col], sc[col]) : 0.f;
+    }));
+    W.param_bytes += (size_t)ne * sizeof(float);
   }
   if (net->D == 3 && K == 27 && L.cin_pad % 16 == 0 && cout % 32 == 0) {
     // second copy in v_mfma_f32_16x16x4_f32 operand order (conv_os.hip): W16[k][g][jb][lane][c]
     const int GT = L.cin_pad / 16, NB = cout / 16;
-    std::vector<float> t16((size_t)K * GT * NB * 256);
-    for (int k = 0; k < K; ++k) {
-      const float *src = kd->data + (size_t)k * cin * cout;
-      for (int g = 0; g < GT; ++g)
-        for (int jb = 0; jb < NB; ++jb)
-          for (int lane = 0; lane < 64; ++lane) {
-            float *d = t16.data() + ((((size_t)k * GT + g) * NB + jb) * 64 + lane) * 4;
-            const int col = 16 * jb + (lane & 15);
-            for (int c = 0; c < 4; ++c) {
-              const int row = 16 * g + 4 * (lane >> 4) + c;
-              d[c] = row < cin ? src[(size_t)row * cout + col] * scale[col] : 0.f;
-            }
-          }
+    {
+      const int64_t ne = (int64_t)K * GT * NB * 256;
+      DGR_CHECK(W.alloc(&L.w16, ne));
+      float *const dst = L.w16;
+      DGR_CHECK(dgr_fill(s, ne, [=] __device__(int64_t o) {
+        const int c = (int)(o & 3), lane = (int)((o >> 2) & 63);
+        const int64_t r = o >> 8;
+        const int jb = (int)(r % NB), g = (int)((r / NB) % GT), k = (int)(r / ((int64_t)NB * GT));
+        const int col = 16 * jb + (lane & 15), row = 16 * g + 4 * (lane >> 4) + c;
+        dst[o] = row < cin ? __fmul_rn(src[((size_t)k * cin + row) * cout + col], sc[col]) : 0.f;
+      }));
+      W.param_bytes += (size_t)ne * sizeof(float);
     }
-    DGR_HIP_CHECK(hipMalloc((void **)&L.w16, t16.size() * sizeof(float)));
-    DGR_HIP_CHECK(hipMemcpy(L.w16, t16.data(), t16.size() * sizeof(float), hipMemcpyHostToDevice));
-    net->W->param_bytes += t16.size() * sizeof(float);
     if (cin % 32 == 0) {
-      // WB[piece][k][s][jb][lane] = 8 bf16 = piece of W[k][32 s + 8 (lane >> 4) + e][16 jb + (lane & 15)]
+      // WB[piece][k][s][jb][lane] = 8 f16 = piece of W[k][32 s + 8 (lane >> 4) + e][16 jb + (lane & 15)]
       const int S32 = cin / 32;
       L.w16b_piece = (int64_t)K * S32 * NB * 64;
-      std::vector<uint16_t> pcs((size_t)2 * L.w16b_piece * 8);
-      for (int k = 0; k < K; ++k) {
-        const float *src = kd->data + (size_t)k * cin * cout;
-        for (int sI = 0; sI < S32; ++sI)
-          for (int jb = 0; jb < NB; ++jb)
-            for (int lane = 0; lane < 64; ++lane) {
-              const int col = 16 * jb + (lane & 15);
-              const size_t o = ((((size_t)k * S32 + sI) * NB + jb) * 64 + lane) * 8;
-              for (int e = 0; e < 8; ++e) {
-                const float xs = src[(size_t)(32 * sI + 8 * (lane >> 4) + e) * cout + col] * scale[col] * w_scale;
-                pcs[o + e] = f16_bits(xs);
-                pcs[(size_t)L.w16b_piece * 8 + o + e] = f16_bits(xs - f16_val(xs));
-              }
-            }
-      }
-      DGR_HIP_CHECK(hipMalloc(&L.w16b, pcs.size() * sizeof(uint16_t)));
-      DGR_HIP_CHECK(hipMemcpy(L.w16b, pcs.data(), pcs.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-      net->W->param_bytes += pcs.size() * sizeof(uint16_t);
+      const int64_t ne = L.w16b_piece * 8;
+      uint16_t *pcs;
+      DGR_CHECK(W.alloc(&pcs, (size_t)2 * ne));
+      L.w16b = pcs;
+      DGR_CHECK(dgr_fill(s, ne, [=] __device__(int64_t o) {
+        const int e = (int)(o & 7), lane = (int)((o >> 3) & 63);
+        const int64_t r = o >> 9;
+        const int jb = (int)(r % NB), sI = (int)((r / NB) % S32), k = (int)(r / ((int64_t)NB * S32));
+        const int col = 16 * jb + (lane & 15), row = 32 * sI + 8 * (lane >> 4) + e;
+        const float xs = __fmul_rn(__fmul_rn(src[((size_t)k * cin + row) * cout + col], sc[col]), w_scale);
+        pcs[o] = dgr_f16_bits_dev(xs);
+        pcs[ne + o] = dgr_f16_bits_dev(xs - dgr_f16_val_dev(xs));
+      }));
+      W.param_bytes += (size_t)2 * ne * sizeof(uint16_t);
       if (net->D == 3 && K == 27 && (dgr_conv_dense_supported(cin, L.cin_pad, cout) || dgr_conv_up_supported(cin, L.cin_pad, cout))) {
-        // (conv_up.hip, the transposed convs' kernel, gathers the same way)
-        // conv_dense.hip reads its weight operands straight from memory: the quad-coalesced gather hands lane (col, lq)
-        // the channels 4 lq .. + 3 and 16 + 4 lq .. + 3 of a 32-channel step, so its 16-byte operand is half (lq & 1) of the
-        // natural fragments of lanes (col, lq >> 1) and (col, (lq >> 1) + 2)
-        std::vector<uint16_t> pd(pcs.size());
-        for (size_t f = 0; f < pcs.size() / 8; ++f) {
-          const size_t base = f & ~(size_t)63;
+        // conv_dense.hip (and conv_up.hip, which gathers the same way) reads its weight operands straight from memory: the
+        // quad-coalesced gather hands lane (col, lq) the channels 4 lq .. + 3 and 16 + 4 lq .. + 3 of a 32-channel step,
+        // so its 16-byte operand is half (lq & 1) of the natural fragments of lanes (col, lq >> 1) and (col, (lq >> 1) + 2)
+        uint16_t *pd;
+        DGR_CHECK(W.alloc(&pd, (size_t)2 * ne));
+        L.w16d = pd;
+        DGR_CHECK(dgr_fill(s, 2 * ne, [=] __device__(int64_t o) {   // (fragments of both pieces alike)
+          const int e = (int)(o & 3), h = (int)((o >> 2) & 1);
+          const int64_t f = o >> 3, base = f & ~(int64_t)63;
           const int lane = (int)(f & 63), col = lane & 15, lq = lane >> 4;
-          for (int h = 0; h < 2; ++h) {
-            const size_t srcf = base + col + 16 * ((lq >> 1) + 2 * h);
-            for (int e = 0; e < 4; ++e) pd[f * 8 + 4 * h + e] = pcs[srcf * 8 + 4 * (lq & 1) + e];
-          }
-        }
-        DGR_HIP_CHECK(hipMalloc(&L.w16d, pd.size() * sizeof(uint16_t)));
-        DGR_HIP_CHECK(hipMemcpy(L.w16d, pd.data(), pd.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        net->W->param_bytes += pd.size() * sizeof(uint16_t);
+          const int64_t srcf = base + col + 16 * ((lq >> 1) + 2 * h);
+          pd[o] = pcs[srcf * 8 + 4 * (lq & 1) + e];
+        }));
+        W.param_bytes += (size_t)2 * ne * sizeof(uint16_t);
       }
     }
   }
@@ -483,39 +336,31 @@ static int make_layer(dgr_net *net, const dgr_weight_desc *descs, int nd, const 
     int ks = 1;
     while (ks * ks * ks < K) ++ks;
     const int ks2 = ks * ks, steps = (ks2 + 3) / 4;
-    std::vector<float> wc((size_t)ks * steps * 64 * 2, 0.f);
-    for (int kz = 0; kz < ks; ++kz)
-      for (int s = 0; s < steps; ++s)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int kk = 4 * s + (lane >> 4);
-          if (kk >= ks2) continue;
-          const int k = kz * ks2 + kk;
-          float *d = wc.data() + (((size_t)kz * steps + s) * 64 + lane) * 2;
-          d[0] = kd->data[(size_t)k * cout + (lane & 15)] * scale[lane & 15];
-          d[1] = kd->data[(size_t)k * cout + 16 + (lane & 15)] * scale[16 + (lane & 15)];
-        }
-    DGR_HIP_CHECK(hipMalloc((void **)&L.wc, wc.size() * sizeof(float)));
-    DGR_HIP_CHECK(hipMemcpy(L.wc, wc.data(), wc.size() * sizeof(float), hipMemcpyHostToDevice));
+    const int64_t ne = (int64_t)ks * steps * 128;
+    DGR_CHECK(W.alloc(&L.wc, ne));
+    float *const dst = L.wc;
+    DGR_CHECK(dgr_fill(s, ne, [=] __device__(int64_t o) {
+      const int j = (int)(o & 1), lane = (int)((o >> 1) & 63);
+      const int64_t r = o >> 7;
+      const int s2 = (int)(r % steps), kz = (int)(r / steps);
+      const int kk = 4 * s2 + (lane >> 4), col = (lane & 15) + 16 * j;
+      dst[o] = kk < ks2 ? __fmul_rn(src[(size_t)(kz * ks2 + kk) * cout + col], sc[col]) : 0.f;
+    }));
   }
   if (name == "conv1" && cin == 6 && cout == 32 && K > 1) {
     // conv_cin6_quad_kernel (conv.hip): wq[k][i][q][e] = W[k][i / 2][8 q + 4 (i % 2) + e], batch norm folded in
-    std::vector<float> wq((size_t)K * 192);
-    for (int k = 0; k < K; ++k)
-      for (int i = 0; i < 12; ++i)
-        for (int q = 0; q < 4; ++q)
-          for (int e = 0; e < 4; ++e) {
-            const int ci = i >> 1, co = 8 * q + 4 * (i & 1) + e;
-            wq[(size_t)k * 192 + (i * 4 + q) * 4 + e] = kd->data[((size_t)k * cin + ci) * cout + co] * scale[co];
-          }
-    DGR_HIP_CHECK(hipMalloc((void **)&L.wq, wq.size() * sizeof(float)));
-    DGR_HIP_CHECK(hipMemcpy(L.wq, wq.data(), wq.size() * sizeof(float), hipMemcpyHostToDevice));
-    net->W->param_bytes += wq.size() * sizeof(float);
+    const int64_t ne = (int64_t)K * 192;
+    DGR_CHECK(W.alloc(&L.wq, ne));
+    float *const dst = L.wq;
+    DGR_CHECK(dgr_fill(s, ne, [=] __device__(int64_t o) {
+      const int e = (int)(o & 3), q = (int)((o >> 2) & 3);
+      const int i = (int)((o >> 4) % 12), k = (int)(o / 192);
+      const int ci = i >> 1, co = 8 * q + 4 * (i & 1) + e;
+      dst[o] = __fmul_rn(src[((size_t)k * cin + ci) * cout + co], sc[co]);
+    }));
+    W.param_bytes += (size_t)ne * sizeof(float);
   }
-  if (has_shift) {
-    DGR_HIP_CHECK(hipMalloc((void **)&L.shift, cout * sizeof(float)));
-    DGR_HIP_CHECK(hipMemcpy(L.shift, shift.data(), cout * sizeof(float), hipMemcpyHostToDevice));
-  }
-  net->W->layers.push_back(L);
+  W.layers.push_back(L);
   return DGR_OK;
 }
 
@@ -538,6 +383,10 @@ static int net_create(dgr_ctx *ctx, int D, int in_channels, int out_channels, in
               "dgr_net_create: unsupported channel counts in=%d out=%d", in_channels, out_channels);
   DGR_REQUIRE(conv1_kernel_size % 2 == 1, "conv1 kernel size must be odd");
   DGR_HIP_CHECK(hipSetDevice(ctx->device));
+  WeightPrep P{dev};
+  DGR_HIP_CHECK(hipStreamCreate(&P.s));
+  DGR_HIP_CHECK(hipMalloc((void **)&P.sc, 256 * sizeof(float)));
+  DGR_HIP_CHECK(hipMalloc((void **)&P.mxb, sizeof(uint32_t)));
   dgr_net *net = new dgr_net();
   net->ctx = ctx;
   net->W = std::make_shared<DgrWeights>();
@@ -548,7 +397,7 @@ static int net_create(dgr_ctx *ctx, int D, int in_channels, int out_channels, in
   for (int d = 0; d < D; ++d) { k3 *= 3; k1 *= conv1_kernel_size; }
   int rc = DGR_OK;
   auto L = [&](const std::string &name, int K, int ci, int co, const char *bn, bool bias = false) {
-    if (rc == DGR_OK) rc = make_layer(net, weights, n_weights, name, K, ci, co, bn, bias, dev);
+    if (rc == DGR_OK) rc = make_layer(net, P, weights, n_weights, name, K, ci, co, bn, bias);
   };
   auto block = [&](const std::string &b, int c) {
     L(b + ".conv1", k3, c, c, (b + ".norm1").c_str());
@@ -563,6 +412,8 @@ static int net_create(dgr_ctx *ctx, int D, int in_channels, int out_channels, in
   L("conv2_tr", k3, CH[2] + TR[3], TR[2], "norm2_tr");  block("block2_tr", TR[2]);
   L("conv1_tr", 1, CH[1] + TR[2], TR[1], nullptr);      // no bias, no BN: residual_block.py:38-44
   L("final", 1, TR[1], out_channels, nullptr, true);    // the only bias: resunet.py:589-596
+  // the caller may free its tensors when the call returns
+  if (rc == DGR_OK) rc = [&] { DGR_HIP_CHECK(hipStreamSynchronize(P.s)); return DGR_OK; }();
   if (rc != DGR_OK) {
     dgr_net_destroy(net);
     return rc;
@@ -696,8 +547,7 @@ struct Fwd {
       o.wb3 = L.w16b; o.piece_stride = L.w16b_piece;
       o.wbd = L.w16d;
       o.w_unscale = L.w_unscale; o.n_in_cap = cin_map.n_cap;
-      static const bool os_f32 = getenv("DGR_EXACT_F32") != nullptr;   // (conv_os.hip reads the same switch)
-      if (L.w16b && !os_f32) {
+      if (L.w16b && !dgr_exact_f32()) {
         o.row_amax = in.amax;
         if (!o.row_amax) {   // a tensor that did not come out of one of the conv kernels (the single-layer debug entry)
           uint32_t *mx;
@@ -901,10 +751,10 @@ int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, 
   if (use_nbr && !getenv("DGR_NO_DSPLIT")) {
     // the middle tensor of a residual block at the two finest levels goes from dense-tile kernel to dense-tile kernel:
     // written as that kernel's operand pieces, and as nothing else (the conditions are those of `o.dense` in Fwd::conv)
-    static const bool os_f32 = getenv("DGR_EXACT_F32") != nullptr, os_lists = getenv("DGR_OS_LISTS") != nullptr;
+    static const bool os_lists = getenv("DGR_OS_LISTS") != nullptr;
     auto dense_layer = [&](int l, int64_t rows) {
       const DgrLayer &L = net->W->layers[l];
-      return L.w16b && L.w16d && !os_f32 && !os_lists && dgr_conv_dense_supported(L.cin, L.cin_pad, L.cout) &&
+      return L.w16b && L.w16d && !dgr_exact_f32() && !os_lists && dgr_conv_dense_supported(L.cin, L.cin_pad, L.cout) &&
              rows * (int64_t)L.cin * 4 < (1ll << 31);
     };
     struct { Tensor *t; int producer; int64_t rows; } mid[] = {{&Y1, 1, n1}, {&Y2, 4, n2}, {&V2, 16, n2}, {&V1, 19, n1}};

@@ -77,8 +77,8 @@ class NetHandle:
         keep, descs = [], []
         items = [(n, t) for n, t in state_dict.items() if not n.endswith('num_batches_tracked')]
         # a state dict that is ALREADY on this device (torch CUDA tensors: e.g. views of the broadcast buffer of a
-        # multi-GPU start, dist.broadcast_checkpoint) stays there: dgr_net_create_device folds / splits / tiles it with
-        # HIP kernels; anything else goes through the host path
+        # multi-GPU start, dist.broadcast_checkpoint) stays there: dgr_net_create_device reads it in place; anything
+        # else goes through dgr_net_create, which uploads it first
         on_device = bool(items) and all(torch.is_tensor(t) and t.is_cuda and t.device.index == (self.device.index or 0)
                                         for _, t in items)
         self.created_on_device = on_device

@@ -90,8 +90,8 @@ int dgr_voxelize(dgr_ctx *ctx, const void *xyz, int is_f64, int64_t M, double vo
  * normalize_feature, D) + load_state_dict + .eval() (core/deep_global_registration.py:96-131;
  * class at model/resunet.py:419-665).  Tensors are HOST float32 arrays in MinkowskiEngine
  * state_dict layout ("conv1.kernel" [K,Cin,Cout], "norm1.bn.weight", ..., "final.bias");
- * the library folds eval-mode batch norm into the kernels, re-tiles them for the MFMA
- * B-operand and copies them to HBM; the caller may free its arrays afterwards.
+ * the library copies them to HBM, folds eval-mode batch norm into the kernels and re-tiles them there
+ * for the MFMA B-operand; the caller may free its arrays afterwards.
  * Offset axis of a kernel: index j = sum_d (delta_d + ks/2) ks^d, FIRST spatial axis fastest; a transposed
  * convolution (conv4_tr / conv3_tr / conv2_tr) pairs index and offset like the forward strided map it swaps -- the
  * library's reading of MinkowskiEngine 0.5.4 (unverifiable offline).  A checkpoint in another convention is
@@ -108,10 +108,9 @@ int dgr_net_create(dgr_ctx *ctx, int D, int in_channels, int out_channels, int c
                    dgr_net **out);
 /* The same with every `data` a DEVICE pointer on the context's device ("host or device pointers"): the state
  * dict is already in HBM -- e.g. views of the flat RCCL broadcast buffer of a multi-GPU start (deepglobalregistration_amd/
- * dist.py) -- and batch-norm folding, the power-of-two weight scale, the f16 split and every MFMA operand layout are
- * produced by HIP kernels from there: nothing but the per-channel batch-norm vectors (cout floats each) travels to the host.
- * Bit-identical weight sets to dgr_net_create on the same values (tests/test_gpu_device_weights.py).  The library copies:
- * the caller may free its tensors when the call returns. */
+ * dist.py) -- and is read from there, not uploaded: nothing but the per-channel batch-norm vectors (cout floats each)
+ * travels to the host.  The weight preparation is dgr_net_create's: bit-identical weight sets on the same values
+ * (tests/test_gpu_device_weights.py).  The library copies: the caller may free its tensors when the call returns. */
 int dgr_net_create_device(dgr_ctx *ctx, int D, int in_channels, int out_channels, int conv1_kernel_size,
                           int normalize_feature, const dgr_weight_desc *weights, int n_weights,
                           dgr_net **out);

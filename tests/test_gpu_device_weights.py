@@ -1,7 +1,7 @@
 """`dgr_net_create_device`: a state dict that is already in HBM (torch CUDA tensors, e.g. views of the RCCL broadcast
-buffer of a multi-GPU start) is folded / split / tiled into the conv kernels' operand layouts by HIP kernels.  The weight
-sets must be the ones `dgr_net_create` builds on the host from the same values: both networks' outputs are compared BIT
-FOR BIT (3-D FCGF net with conv1 k = 7 and k = 5 -- every 3-D layout incl. the value-grid conv1 --, 6-D inlier net -- the
+buffer of a multi-GPU start) is read in place by the weight preparation.  The weight sets must be the ones
+`dgr_net_create` builds from the same values uploaded from the host: both networks' outputs are compared BIT FOR BIT
+(3-D FCGF net with conv1 k = 7 and k = 5 -- every 3-D layout incl. the value-grid conv1 --, 6-D inlier net -- the
 wide-layer pieces, the quad-major conv1, the f32 tiles)."""
 import numpy as np
 import pytest
