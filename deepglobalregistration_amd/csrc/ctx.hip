@@ -15,7 +15,7 @@ void dgr_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *dgr_last_error(void) { return g_err; }
-extern "C" const char *dgr_version(void) { return "dgr_hip 0.3 (gfx950)"; }
+extern "C" const char *dgr_version(void) { return "dgr_hip 0.4 (gfx950)"; }
 
 // ------------------------------------------------------------------------------------------
 // arena: sized for 288 GB of HBM -- worst-case kernel-map capacities are reserved instead of

@@ -13,21 +13,7 @@
 // Batched (round 5): every kernel below runs ONCE for all pairs of a batch -- blockIdx.z (packing: blockIdx.y) selects
 // the pair, whose row ranges inside the concatenated feature matrices come from a by-value descriptor table -- instead
 // of 13 launches per pair in a host loop; reference indices are written as rows of the concatenated F1.
-#include "dgr_internal.h"
-
-constexpr int KNN_THREADS = 256;
-constexpr int KNN_TB = 64;  // F1 rows per LDS tile
-constexpr int KNN_MAXP = 32;   // pairs per launch (descriptor table passed by value: no upload, no host buffer to keep alive)
-
-struct KnnPair {
-  int64_t q0, r0;      // first query row (of F0) / first reference row (of F1) of the pair
-  int32_t n0, n1;      // queries / references
-  int32_t qb0, rt0;    // first 32-row block of the pair in the packed query / reference arrays
-};
-struct KnnBatch {
-  KnnPair p[KNN_MAXP];
-  int np;
-};
+#include "knn_common.h"
 
 template <int C, int QPT>
 __global__ void __launch_bounds__(KNN_THREADS)
@@ -178,29 +164,11 @@ static int knn_launch(dgr_ctx *ctx, const float *F0, const float *F1, const KnnB
 // a non-finite / huge feature makes the brute-force kernel, launched behind, redo the pair's whole search.  No host
 // round trip either way.
 // ------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-constexpr float KNN_TAU_C = 8e-5f;  // 2 c
 constexpr int KNN_SLOTS = 32;       // candidate slots per query (every 2nd stage sampled: at most 16 seen on the benchmark's features)
 #ifndef DGR_KNN_SUB
 #define DGR_KNN_SUB 2
 #endif
 constexpr int KNN_SUB = DGR_KNN_SUB;   // pass 1 visits every KNN_SUB-th group of KNN_ST reference tiles (1: all of them)
-
-__device__ __forceinline__ unsigned short knn_f2bf(float x) {  // round to nearest even
-  uint32_t u = __float_as_uint(x);
-  if ((u & 0x7f800000u) == 0x7f800000u) return (unsigned short)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-__device__ __forceinline__ float knn_bf2f(unsigned short h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint32_t knn_ord(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float knn_unord(uint32_t k) {
-  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
-}
 
 // packed[(tile * 4 + f) * 64 + r + 32 g] = 8 bf16: dims 16 (f & 1) + 8 g .. + 7 of row 32 tile + r,
 // f >> 1 = 0: hi, 1: lo.  One thread per (row, g, chunk); the (g = 0, chunk = 0) thread also writes the norm.
@@ -210,10 +178,12 @@ __device__ __forceinline__ float knn_unord(uint32_t k) {
 // every subset of tiles, the sample of pass 1 in particular -- is spread evenly over the cloud.  (Consecutive rows are
 // neighbouring voxels with similar descriptors: a sample of whole 128-row stages in row order misses whole
 // neighbourhoods, and then every member of the true neighbour's cluster lies under the sampled minimum.)
+// skew = 1 (the top-k search, knn_topk.hip) rotates the row blocks per tile: slot s of tile t holds row
+// ((s + t) mod 32) n_tiles + t, so that every SLOT, too, is spread over the cloud; skew = 0 is the layout above.
 __global__ void __launch_bounds__(256)
     knn_pack_kernel(const float *__restrict__ F0, const float *__restrict__ F1, KnnBatch B,
                     bf16x8 *__restrict__ Qp, bf16x8 *__restrict__ Rp, float *__restrict__ na, float *__restrict__ nb,
-                    uint32_t *__restrict__ nb_max, int32_t *__restrict__ fallback) {
+                    uint32_t *__restrict__ nb_max, int32_t *__restrict__ fallback, int skew) {
   const int pair = blockIdx.y >> 1, side = blockIdx.y & 1;
   const KnnPair d = B.p[pair];
   const int64_t N = side ? d.n1 : d.n0;
@@ -224,7 +194,7 @@ __global__ void __launch_bounds__(256)
   const float *F = side ? F1 + d.r0 * 32 : F0 + d.q0 * 32;
   const float scale = side ? -2.f : 1.f;
   const int64_t prow = row;                                   // position in the packed array
-  if (side) row = (prow & 31) * (n_pad >> 5) + (prow >> 5);   // the reference row that sits there
+  if (side) row = (((prow & 31) + skew * (prow >> 5)) & 31) * (n_pad >> 5) + (prow >> 5);   // the reference row that sits there
   bf16x8 *packed = side ? Rp + (int64_t)d.rt0 * 256 : Qp + (int64_t)d.qb0 * 256;
   float *norms = side ? nb + (int64_t)d.rt0 * 32 : na + (int64_t)d.qb0 * 32;
   const int g = (int)(t & 1), ch = (int)((t >> 1) & 1);
@@ -270,7 +240,6 @@ __global__ void __launch_bounds__(256)
 // version ran the L1 at ~2/3 of its bandwidth with four identical request streams).
 // Grid: x = groups of 16 query blocks (of the largest pair), y = reference splits, z = pair.  PASS2 = false walks
 // every KNN_SUB-th stage of its split only (the sample), PASS2 = true every stage.
-constexpr int KNN_ST = 4;
 template <bool PASS2>
 __global__ void __launch_bounds__(256, 2)
     knn_mfma_kernel(const bf16x8 *__restrict__ Qp, const bf16x8 *__restrict__ Rp, const float *__restrict__ nbp,
@@ -399,6 +368,14 @@ __global__ void __launch_bounds__(256, 2)
       if (lane < 32 && qb0 + u < n_qblocks && q < N0) atomicMin(mt + q, knn_ord(mm));
     }
   }
+}
+
+int knn_pack(const float *F0, const float *F1, const KnnBatch &B, int rows_max, int skew, bf16x8 *Qp, bf16x8 *Rp,
+             float *na, float *nb, uint32_t *nb_max, int32_t *fallback, hipStream_t stream) {
+  dim3 grid((unsigned)dgr_ceil_div((int64_t)rows_max * 4, 256), 2 * B.np);
+  knn_pack_kernel<<<grid, 256, 0, stream>>>(F0, F1, B, Qp, Rp, na, nb, nb_max, fallback, skew);
+  DGR_LAUNCH_CHECK();
+  return DGR_OK;
 }
 
 // one thread per query of the batch walks its candidate slots (two on average); candidates are rows of the concatenated F1
@@ -559,7 +536,7 @@ static int knn_prefiltered(dgr_ctx *ctx, const float *F0, const float *F1, KnnBa
   {
     const int rows_max = std::max(qb_max, rt_max) * 32;
     dim3 grid((unsigned)dgr_ceil_div((int64_t)rows_max * 4, 256), 2 * B.np);
-    knn_pack_kernel<<<grid, 256, 0, stream>>>(F0, F1, B, Qp, Rp, na, nb, nb_max, fallback);
+    knn_pack_kernel<<<grid, 256, 0, stream>>>(F0, F1, B, Qp, Rp, na, nb, nb_max, fallback, 0);
     DGR_LAUNCH_CHECK();
   }
   int qgroups_all = 0;

@@ -179,6 +179,24 @@ int dgr_knn1_l2_batch(dgr_ctx *ctx, const float *F0, const int64_t *off0, const 
                       const int64_t *off1, int npairs, int C, int squared, int64_t *idx_out,
                       float *dist_out, dgr_stream stream);
 
+/* ---- feature-space k-NN: replaces core.knn.find_knn_gpu(F0, F1, nn_max_n > 1, knn=k, return_distance)
+ * (core/knn.py:23-74, the chunked branch that honours knn).  F0 / F1 as for dgr_knn1_l2; 1 <= k <=
+ * DGR_KNN_MAX_K, anything else is DGR_EINVAL.  idx_out dev int64 [N0,k], dist_out dev f32 [N0,k] or NULL,
+ * row-major; row i ascending by f32 sum (a-b)^2, equal distances by the smaller index, column 0 = the
+ * dgr_knn1_l2 result bit for bit (k = 1 is that call).  Columns j >= N1: index 0, distance inf (the
+ * reference's repeated min on an exhausted row).  squared as for dgr_knn1_l2. */
+#define DGR_KNN_MAX_K 32
+int dgr_knn_l2(dgr_ctx *ctx, const float *F0, int64_t N0, const float *F1, int64_t N1, int C, int k,
+               int squared, int64_t *idx_out, float *dist_out, dgr_stream stream);
+
+/* ---- the same k-NN search for every pair of a collated batch: replaces core.knn.find_knn_gpu_batch(F0, F1,
+ * len_batch, nn_max_n > 1, knn=k, ...) (core/knn.py:106-140).  F0 / F1 / off0 / off1 as for
+ * dgr_knn1_l2_batch; idx_out dev int64 [off0[npairs],k]: rows of the CONCATENATED F1 (padding columns of pair p
+ * hold off1[p], the reference's `concat_results` numbering); dist_out dev f32 [off0[npairs],k] or NULL. */
+int dgr_knn_l2_batch(dgr_ctx *ctx, const float *F0, const int64_t *off0, const float *F1,
+                     const int64_t *off1, int npairs, int C, int k, int squared, int64_t *idx_out,
+                     float *dist_out, dgr_stream stream);
+
 /* ---- 6-D inlier-network input: replaces the torch.cat at core/deep_global_registration.py:261-262
  * and inlier_feature_generation (:185-208).  idx1 dev int64 [N0] (corres_idx1; corres_idx0 is
  * arange(N0)).  feature_type 0='ones' -> feats [N0,1]; 1='coords' -> [N0,6] =
