@@ -32,7 +32,7 @@ if [ "$1" != nopmc ]; then
   python $R/tools/pmc_dominant.py "reduce_rows_kernel<64" "$W" $DBS > $O/reduce_rows_pmc.json
   python $R/tools/pmc_dominant.py "sparse_conv_wide_f16x2<64, 1, 2>" "$W" $DBS > $O/wide64_pmc.json
   python $R/tools/pmc_dominant.py "conv1_grid_mfma" "$W" $DBS > $O/conv1_pmc.json
-  python $R/tools/pmc_dominant.py "knn_mfma_kernel<true>" "$W" $DBS > $O/knn_pmc.json
+  python $R/tools/pmc_dominant.py "knn_mfma_kernel<true, false>" "$W" $DBS > $O/knn_pmc.json
   python $R/tools/pmc_dominant.py "registration_kernel" "$W" $DBS > $O/registration_pmc.json
   python - <<P
 import json
