@@ -257,12 +257,8 @@ class DeepGlobalRegistration:
                                        forced_logits=forced_logits, skip_refinement=skip_refinement,
                                        safeguard=safeguard, icp=icp)
 
-    def register_collated(self, input_dict, **kw):
-        """Registers every pair of a collated batch in the reference's data-loader layout
-        (`CollationFunctionFactory.collate_pair_fn`, dataloader/base_loader.py:40-98): `sinput0_C` /
-        `sinput1_C` int [N,4] batched coordinates (batch column first, `ME.utils.batched_coordinates`),
-        `pcd0` / `pcd1` sequences of per-pair xyz [Ni,3] aligned with those rows, `len_batch` [[N0,N1],...].
-        Returns T [n,4,4] float64, status [n], stats [n,4]."""
+    def _collated(self, input_dict):
+        """(coords0, xyz0, off0, coords1, xyz1, off1) of a collated batch on the device, checked against `len_batch`."""
         len_batch = [(int(a), int(b)) for a, b in input_dict['len_batch']]
         off0, off1 = [0], [0]
         for n0, n1 in len_batch:
@@ -277,7 +273,15 @@ class DeepGlobalRegistration:
         for p in range(len(len_batch)):   # the batch column must be the pair index of the row block
             if off0[p + 1] > off0[p] and (int(c0[off0[p], 0]) != p or int(c0[off0[p + 1] - 1, 0]) != p):
                 raise ValueError('sinput0_C is not in batched_coordinates order')
-        return self.register_voxelized(c0, x0, off0, c1, x1, off1, **kw)
+        return c0, x0, off0, c1, x1, off1
+
+    def register_collated(self, input_dict, **kw):
+        """Registers every pair of a collated batch in the reference's data-loader layout
+        (`CollationFunctionFactory.collate_pair_fn`, dataloader/base_loader.py:40-98): `sinput0_C` /
+        `sinput1_C` int [N,4] batched coordinates (batch column first, `ME.utils.batched_coordinates`),
+        `pcd0` / `pcd1` sequences of per-pair xyz [Ni,3] aligned with those rows, `len_batch` [[N0,N1],...].
+        Returns T [n,4,4] float64, status [n], stats [n,4]."""
+        return self.register_voxelized(*self._collated(input_dict), **kw)
 
     def register_voxelized(self, coords0, xyz0, off0, coords1, xyz1, off1, forced_logits=None,
                            skip_refinement=False, override_idx1=None, safeguard=False, icp=False):
@@ -296,3 +300,69 @@ class DeepGlobalRegistration:
             ransac_seed=self.ransac_seed)
         T = T.astype(np.float64)   # (already float64 when the safeguard / ICP stages ran: their results at full width)
         return T, status, stats
+
+    # ---- measurement beside the registration path (core/trainer.py:353-489, `_valid_epoch`) ----------------------
+    def validate_collated(self, input_dict, matching_radius=None, success_rte_thresh=0.3, success_rre_thresh=15.0, **kw):
+        """The validation statistics of the reference's trainer for one collated batch (layout of `register_collated`) that
+        also carries `T_gt` [n,4,4]: how good the feature matches and the inlier weights are against the ground-truth
+        pose.  Read-only beside registration: the batch goes through `register_voxelized(..., skip_refinement=True, **kw)`
+        (the harness hooks `forced_logits` / `override_idx1` pass through), then
+          * positive pairs: `input_dict['correspondences']` (one [P,2] array per pair) when present, otherwise every
+            (i, j) within `matching_radius` (default 2 voxels) under T_gt (ops.radius_pairs_batch);
+          * a match (i, idx1[i]) is correct when it is a positive pair (ops.pairs_isin, seed max(N0, N1));
+          * (n, hits, tp, fp, tn, fn) per pair at weight > 0.5 (ops.validation_counts);
+          * the weighted-Procrustes pose of every pair whatever the confidence gate said (`_valid_epoch` does not gate),
+            `valid = wsum > 10` (:417), success = RTE and RRE below the thresholds and valid.
+        Returns a dict with the reference's keys (hit_ratio, precision, recall, f1, tpr, tnr, balanced_accuracy with its
+        eps; regist_rte, regist_rre, succ_rate: means over the pairs) and the per-pair arrays `counts` [n,6], `rte`, `rre`,
+        `success`, `valid`, `wsum`, `T_pred` [n,4,4], `num_pos_pairs`."""
+        from ..eval.metrics import batch_rte_rre, validation_statistics
+        c0, x0, off0, c1, x1, off1 = self._collated(input_dict)
+        n = len(off0) - 1
+        T_gt = input_dict['T_gt']
+        T_gt = (T_gt.detach().cpu().numpy() if torch.is_tensor(T_gt) else np.asarray(T_gt)).astype(np.float64)
+        if T_gt.shape != (n, 4, 4):
+            raise ValueError(f'T_gt must be [{n},4,4], got {T_gt.shape}')
+        radius = 2 * self.voxel_size if matching_radius is None else matching_radius
+        if input_dict.get('correspondences') is None:
+            ops.check_radius_args(radius, None, T_gt, n)          # fail before the networks run
+        kw = dict(kw, skip_refinement=True)
+        _, _, stats = self.register_voxelized(c0, x0, off0, c1, x1, off1, **kw)
+        idx1 = ops.batch_output(self.device, 'idx1')              # rows of the concatenated fragment 1
+        weights = ops.batch_output(self.device, 'weights')
+        o0, o1 = np.asarray(off0, np.int64), np.asarray(off1, np.int64)
+        seg = torch.repeat_interleave(torch.arange(n, device=self.device), torch.from_numpy(np.diff(o0)).to(self.device))
+        rows = torch.arange(len(idx1), device=self.device)
+        pred = torch.stack((rows - torch.from_numpy(o0).to(self.device)[seg],
+                            idx1 - torch.from_numpy(o1).to(self.device)[seg]), 1)     # pair-local (i, j), trainer.find_pairs
+        if input_dict.get('correspondences') is not None:
+            parts = [torch.as_tensor(np.asarray(p) if not torch.is_tensor(p) else p).reshape(-1, 2).to(self.device, torch.int64)
+                     for p in input_dict['correspondences']]
+            if len(parts) != n:
+                raise ValueError('one correspondence array per pair expected')
+            pos, pos_off = torch.cat(parts), np.cumsum([0] + [len(p) for p in parts])
+        else:
+            pos, pos_off = ops.radius_pairs_batch(x0, o0, x1, o1, T_gt, radius)
+        seeds = [max(int(o0[p + 1] - o0[p]), int(o1[p + 1] - o1[p])) for p in range(n)]
+        label = ops.pairs_isin(pos, pos_off, pred, o0, seeds)
+        counts = ops.validation_counts(label, weights, o0, 0.5)
+        T_pred = np.tile(np.eye(4), (n, 1, 1))
+        solved = np.ones(n, bool)
+        for p in range(n):
+            a, b = int(o0[p]), int(o0[p + 1])
+            try:
+                R, t = ops.weighted_procrustes(x0[a:b], ops.gather_rows3(x1, idx1[a:b]), weights[a:b])
+                T_pred[p, :3, :3], T_pred[p, :3, 3] = R, t
+            except _lib.DgrError as e:      # non-finite input / SVD failure: no pose for this pair
+                if e.code != _lib.DGR_ESVD:
+                    raise
+                solved[p] = False
+        wsum = np.asarray(stats[:, 3], np.float64)
+        valid = (wsum > 10) & solved
+        rte, rre = batch_rte_rre(T_pred[:, :3, :3], T_pred[:, :3, 3], T_gt)
+        success = (rte < success_rte_thresh) & (rre < success_rre_thresh) & valid
+        out = validation_statistics(counts)
+        out.update(regist_rte=float(rte.mean()), regist_rre=float(rre.mean()), succ_rate=float(success.mean()),
+                   counts=counts, rte=rte, rre=rre, success=success, valid=valid, wsum=wsum, T_pred=T_pred,
+                   num_pos_pairs=np.diff(pos_off))
+        return out

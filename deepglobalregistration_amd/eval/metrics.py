@@ -12,3 +12,34 @@ def rte_rre(T_pred, T_gt, rte_thresh, rre_thresh, eps=1e-16):
     cos = (np.trace(T_pred[:3, :3].T @ T_gt[:3, :3]) - 1.0) / 2.0
     rre = float(np.degrees(np.arccos(np.clip(cos, -1 + eps, 1 - eps))))
     return np.array([float(rte < rte_thresh and rre < rre_thresh), rte, rre])
+
+
+VALID_EPS = float(np.finfo(float).eps)   # core/trainer.py:34
+
+
+def validation_statistics(counts, eps=VALID_EPS):
+    """The inlier statistics of core/trainer.py:395, 443-448 (`_valid_epoch`) from validation counts [..., 6] =
+    (n, hits, tp, fp, tn, fn) per batch entry (ops.validation_counts), summed over the entries like the reference's
+    running tp / fp / tn / fn: hit_ratio = hits / n, precision, recall, f1, tpr, tnr, balanced_accuracy, with the
+    reference's eps in every denominator."""
+    c = np.asarray(counts, np.int64).reshape(-1, 6).sum(0)
+    n, hits, tp, fp, tn, fn = (int(v) for v in c)
+    precision = tp / (tp + fp + eps)
+    recall = tp / (tp + fn + eps)
+    f1 = 2 * (precision * recall) / (precision + recall + eps)
+    tpr = tp / (tp + fn + eps)
+    tnr = tn / (tn + fp + eps)
+    return {'hit_ratio': hits / n if n else 0.0, 'precision': precision, 'recall': recall, 'f1': f1, 'tpr': tpr, 'tnr': tnr,
+            'balanced_accuracy': (tpr + tnr) / 2}
+
+
+def batch_rte_rre(R_pred, t_pred, T_gt):
+    """core/metrics.py:25-43 as `_valid_epoch` uses them (core/trainer.py:418-420): per batch entry the translation error
+    |t_pred - t_gt| and the rotation error arccos(clamp((tr(R_pred^T R_gt) - 1) / 2, -0.999, 0.999)) in degrees -- the
+    reference's clamp, so a perfect rotation reads 2.56 degrees, not 0.  The ground truth is rounded to float32 as there."""
+    R_pred, t_pred = np.asarray(R_pred, np.float64).reshape(-1, 3, 3), np.asarray(t_pred, np.float64).reshape(-1, 3)
+    T_gt = np.asarray(T_gt, np.float32).astype(np.float64).reshape(-1, 4, 4)
+    side = ((R_pred * T_gt[:, :3, :3]).sum((1, 2)) - 1) / 2
+    rre = np.degrees(np.arccos(np.clip(side, -0.999, 0.999)))
+    rte = np.linalg.norm(t_pred - T_gt[:, :3, 3], axis=1)
+    return rte, rre

@@ -457,6 +457,123 @@ def ransac_correspondence(X, Y, distance_threshold, num_hypotheses, seed=0):
 
 
 # ----------------------------------------------------------------------------
+# ground-truth matches and validation counts (csrc/gtmatch.hip).  Every argument check below runs on the host values
+# alone, BEFORE a tensor is moved or the library context is created.
+def _offsets(off, name, total=None):
+    o = np.ascontiguousarray(np.asarray(off), dtype=np.int64).reshape(-1)
+    if len(o) < 2 or o[0] != 0 or bool((np.diff(o) < 0).any()):
+        raise ValueError(f'{name} must be [npairs+1] row offsets that start at 0 and do not decrease')
+    if total is not None and o[-1] != total:
+        raise ValueError(f'{name} ends at {int(o[-1])}, the array has {int(total)} rows')
+    return o
+
+
+def _rows(a, width, name):
+    shape = tuple(a.shape) if hasattr(a, 'shape') else np.asarray(a).shape
+    if len(shape) != 2 or shape[1] != width:
+        raise ValueError(f'{name} must be [N,{width}], got {shape}')
+    return shape[0]
+
+
+def check_radius_args(radius, K, T, npairs):
+    """(radius, K as the C ABI wants it, T float64 [npairs,16]); ValueError for a radius that is not a positive finite
+    number, a K that is neither None nor an integer >= 1 (the reference slices idx[:K]), a T that is not [npairs,4,4]
+    (or one [4,4] for one pair) of finite numbers."""
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(radius) or radius <= 0:
+        raise ValueError(f'radius must be a positive finite number, got {radius!r}')
+    if K is not None and (isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or K < 1
+                          or K > np.iinfo(np.int32).max):
+        raise ValueError(f'K must be None or an integer >= 1, got {K!r}')
+    T = T.detach().cpu().numpy() if torch.is_tensor(T) else np.asarray(T)
+    if T.shape == (4, 4) and npairs == 1:
+        T = T[None]
+    if T.shape != (npairs, 4, 4):
+        raise ValueError(f'T must be [{npairs},4,4], got {T.shape}')
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(npairs, 16)
+    if not np.isfinite(T).all():
+        raise ValueError('T must be finite')
+    return float(radius), 0 if K is None else int(K), T
+
+
+def radius_pairs_batch(xyz0, off0, xyz1, off1, T, radius, K=None):
+    """Ground-truth correspondences of every pair of a batch (dgr_radius_pairs_batch): pair p = rows off0[p]:off0[p+1] of
+    xyz0 under the pose T[p] against rows off1[p]:off1[p+1] of xyz1.  Returns (pairs int64 [P,2] on the device: pair-local
+    (i, j) with |T x0[i] - x1[j]| < radius, by i and then by (distance, j), the first K of every i; pair_off int64 numpy
+    [npairs+1]: pair p owns pairs[pair_off[p]:pair_off[p+1]])."""
+    n0, n1 = _rows(xyz0, 3, 'xyz0'), _rows(xyz1, 3, 'xyz1')
+    o0, o1 = _offsets(off0, 'off0', n0), _offsets(off1, 'off1', n1)
+    if len(o0) != len(o1):
+        raise ValueError('off0 and off1 must describe the same number of pairs')
+    npairs = len(o0) - 1
+    radius, K, T = check_radius_args(radius, K, T, npairs)
+    lib = _lib.load()
+    xyz0 = _xyz_dev(xyz0)
+    dev = xyz0.device
+    xyz1 = _xyz_dev(xyz1, dev)
+    counts = torch.empty(n0, dtype=torch.int32, device=dev)
+    total = C.c_int64(0)
+
+    def call(pairs, capacity):
+        check(lib.dgr_radius_pairs_batch(get_ctx(dev), ptr(xyz0), o0.ctypes.data_as(_lib.c_i64p), ptr(xyz1),
+                                         o1.ctypes.data_as(_lib.c_i64p), npairs, T.ctypes.data_as(_lib.c_f64p), radius, K,
+                                         ptr(counts), ptr(pairs), capacity, C.byref(total), stream_ptr(dev.index)))
+    call(None, 0)
+    pairs = torch.empty((total.value, 2), dtype=torch.int64, device=dev)
+    if total.value:
+        call(pairs, total.value)
+    # pairs of every batch entry: the row counts summed over the entry's rows (bookkeeping on npairs + 1 numbers)
+    csum = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), counts.cumsum(0, dtype=torch.int64)])
+    pair_off = csum[torch.from_numpy(o0).to(dev)].cpu().numpy()
+    return pairs, pair_off
+
+
+def radius_pairs(xyz0, xyz1, T, radius, K=None):
+    """One pair: int64 [P,2] (i, j) with |T x0[i] - x1[j]| < radius, the reference's get_matching_indices order."""
+    return radius_pairs_batch(xyz0, [0, _rows(xyz0, 3, 'xyz0')], xyz1, [0, _rows(xyz1, 3, 'xyz1')], T, radius, K)[0]
+
+
+def pairs_isin(pos, pos_off, pred, pred_off, M):
+    """Correctness label of every predicted pair (dgr_pairs_isin_batch): uint8 [Q] on the device, 1 where
+    pred[:,0] + pred[:,1] * M[p] occurs among pos[:,0] + pos[:,1] * M[p] of the same batch entry p (wrapping int64).
+    pos int64 [P,2], pred int64 [Q,2], pos_off / pred_off [npairs+1], M one integer per batch entry."""
+    P, Q = _rows(pos, 2, 'pos'), _rows(pred, 2, 'pred')
+    po, qo = _offsets(pos_off, 'pos_off', P), _offsets(pred_off, 'pred_off', Q)
+    Ms = np.ascontiguousarray(np.asarray(M), dtype=np.int64).reshape(-1)
+    if len(po) != len(qo) or len(Ms) != len(po) - 1:
+        raise ValueError('pos_off, pred_off and M must describe the same number of pairs')
+    lib = _lib.load()
+    dev = _dev(pred)
+    pos, pred = _as(pos, torch.int64, dev), _as(pred, torch.int64, dev)
+    out = torch.empty(Q, dtype=torch.uint8, device=dev)
+    check(lib.dgr_pairs_isin_batch(get_ctx(dev), ptr(pos), po.ctypes.data_as(_lib.c_i64p), ptr(pred),
+                                   qo.ctypes.data_as(_lib.c_i64p), len(Ms), Ms.ctypes.data_as(_lib.c_i64p), ptr(out),
+                                   stream_ptr(dev.index)))
+    return out
+
+
+def validation_counts(label, weights, off, threshold=0.5):
+    """Per batch entry (n, hits, tp, fp, tn, fn) as int64 numpy [npairs,6] (dgr_validation_counts): label uint8 / bool [Q],
+    weights f32 [Q], prediction = weight > threshold."""
+    Q = int(label.shape[0]) if hasattr(label, 'shape') and len(label.shape) >= 1 else -1
+    if Q < 0 or int(np.prod(tuple(label.shape))) != Q or int(np.prod(tuple(weights.shape))) != Q:
+        raise ValueError('label and weights must hold one entry per predicted pair')
+    o = _offsets(off, 'off', Q)
+    if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)) \
+            or np.isnan(threshold):
+        raise ValueError(f'threshold must be a number, got {threshold!r}')
+    lib = _lib.load()
+    dev = _dev(weights)
+    label = _as(label, torch.uint8, dev).reshape(-1)
+    weights = _as(weights, torch.float32, dev).reshape(-1)
+    out = np.zeros((len(o) - 1, 6), np.int64)
+    check(lib.dgr_validation_counts(get_ctx(dev), ptr(label), ptr(weights), float(threshold),
+                                    o.ctypes.data_as(_lib.c_i64p), len(o) - 1, out.ctypes.data_as(_lib.c_i64p),
+                                    stream_ptr(dev.index)))
+    return out
+
+
+# ----------------------------------------------------------------------------
 def register_batch(fcgf, inlier, coords0, xyz0, off0, coords1, xyz1, off1, voxel_size,
                    clip_weight_thresh=0.05, inlier_feature_type='coords', max_iter=1000,
                    max_break_count=20, break_threshold_ratio=1e-4, skip_refinement=False,

@@ -323,6 +323,42 @@ int dgr_ctx_conv_launch_kernel_us(dgr_ctx *ctx, float *us, int64_t capacity, int
  * newline-separated and NUL-terminated in buf; *n = number of names written */
 int dgr_ctx_conv_launch_kinds(dgr_ctx *ctx, char *buf, int64_t capacity, int64_t *n);
 
+/* ---- measurement beside the registration path: what the reference computes on the host to judge its networks
+ * (core/trainer.py:353-489, _valid_epoch).  Read-only: none of the three calls changes what dgr_register_batch computes;
+ * like every top-level call they reuse the context's workspace, so fetch dgr_register_batch_output first.
+ *
+ * Ground-truth correspondences: replaces util.pointcloud.get_matching_indices(source, target, trans, search_voxel_size, K)
+ * (util/pointcloud.py:83-96) for every pair of a collated batch in the same launches.  Pair p uses rows
+ * [off0[p], off0[p+1]) of xyz0 and [off1[p], off1[p+1]) of xyz1 (dev f32 [*,3]; HOST offsets as for dgr_knn_l2_batch, but
+ * a pair may be empty) and the pose T[p] (HOST f64 [npairs,16], row-major 4x4, last row ignored).  For every source row i:
+ * every target row j with d^2 = |R x0[i] + t - x1[j]|^2 < radius^2, STRICTLY, in float64 on the f32 points widened
+ * exactly.  Output rows (i, j), pair-local indices, ordered by i and within one i ascending by (d^2, j); with K > 0 only
+ * the first K of every i (the reference's idx[:K] on Open3D's distance-sorted radius result; Open3D is absent here: the
+ * strict test and the order restate KDTreeFlann.search_radius_vector_3d, ties by index are this library's).  Rows with a
+ * non-finite coordinate, on either side, take no part.
+ * counts_out dev int32 [off0[npairs]]: pairs of every source row (after the cap).  pairs_out dev int64 [capacity,2] or
+ * NULL: NULL returns the counts and *total_out only; a capacity below the total is DGR_EINVAL, never a truncation.
+ * *total_out HOST int64: pairs of the batch.  DGR_EINVAL before any device work: radius <= 0 or not finite, K < 0
+ * (0 = no cap), offsets that do not start at 0 or decrease, a non-finite T.  Synchronises. */
+int dgr_radius_pairs_batch(dgr_ctx *ctx, const float *xyz0, const int64_t *off0, const float *xyz1,
+                           const int64_t *off1, int npairs, const double *T, double radius, int K,
+                           int32_t *counts_out, int64_t *pairs_out, int64_t capacity, int64_t *total_out,
+                           dgr_stream stream);
+/* Correctness labels: replaces core.correspondence.find_correct_correspondence(pos_pairs, pred_pairs, hash_seed,
+ * len_batch) (core/correspondence.py:14-53).  pos dev int64 [pos_off[npairs],2], pred dev int64 [pred_off[npairs],2]
+ * (the pairs' lists back to back, HOST offsets), M_per_pair HOST int64 [npairs] (the reference's hash seed:
+ * max(N0, N1) by default).  out dev uint8 [pred_off[npairs]]: 1 where pred[:,0] + pred[:,1] * M (wrapping int64, numpy's
+ * arithmetic) occurs among the keys of the pair's positive pairs computed the same way -- np.isin on _hash, the
+ * reference's collisions under a small seed included.  Synchronises. */
+int dgr_pairs_isin_batch(dgr_ctx *ctx, const int64_t *pos, const int64_t *pos_off, const int64_t *pred,
+                         const int64_t *pred_off, int npairs, const int64_t *M_per_pair, uint8_t *out,
+                         dgr_stream stream);
+/* Validation counts: replaces is_correct.sum() and the tp / fp / tn / fn bookkeeping at core/trainer.py:395, 430-437.
+ * label dev uint8 [off[npairs]], weights dev f32 [off[npairs]], pred = weight > threshold (0.5 in the reference; a NaN
+ * weight predicts negative), off HOST int64 [npairs+1].  counts_out HOST int64 [npairs,6] = (n, hits, tp, fp, tn, fn).
+ * Integer sums only: bitwise reproducible.  Synchronises. */
+int dgr_validation_counts(dgr_ctx *ctx, const uint8_t *label, const float *weights, float threshold,
+                          const int64_t *off, int npairs, int64_t *counts_out, dgr_stream stream);
 
 /* ---- debug entry points (parity tests): the device functions of the registration kernel on their own.
  * ortho2rotation (core/registration.py:16-64) forward for n parameter rows p6 [n,6] -> R9_out [n,9] (row-major 3x3) and,

@@ -1,6 +1,7 @@
 """Which MinkowskiEngine conventions was a checkpoint written under?  (deepglobalregistration_amd/model/me_conventions.py)
 
     python tools/check_me_conventions.py --weights ckpt.pth --pcd0 a.ply --pcd1 b.ply
+    python tools/check_me_conventions.py --weights ckpt.pth --pcd0 a.ply --pcd1 b.ply --gt T_gt.txt
     python tools/check_me_conventions.py --synthetic          # dry run of the tool itself: no convention can stand out
 
 Registers one real pair under the four combinations of {kernel offsets: first / last axis fastest} x {transposed
@@ -10,6 +11,11 @@ of confident weights.  Under a wrong reading the FCGF features are noise (few ge
 the inlier network has nothing to be confident about; under the right one an overlapping pair passes the gate with a
 large margin.  The default (first axis fastest, same index) is the library's reading of ME 0.5.4; the two keys go into
 the runtime config (`me_kernel_order`, `me_transposed_mirrored`) if another combination wins.
+
+"Consistent with the estimated pose" is circular when the estimate itself is wrong.  With `--gt` (a text file holding
+the 4x4 ground-truth pose that moves pcd0 onto pcd1) every row also reports what the reference's validation measures
+(core/trainer.py:353-489): the hit ratio of the feature matches against the ground-truth correspondences within two
+voxels, and precision / recall of the inlier weights at 0.5 -- and the winner is the reading with the best hit ratio.
 """
 import argparse
 import itertools
@@ -28,11 +34,20 @@ def main():
     ap.add_argument('--pcd0')
     ap.add_argument('--pcd1')
     ap.add_argument('--synthetic', action='store_true')
+    ap.add_argument('--gt', help='text file with the 4x4 ground-truth pose (pcd0 -> pcd1): adds hit ratio, precision, recall')
     args = ap.parse_args()
     from deepglobalregistration_amd import ops, synth
     from deepglobalregistration_amd.core.deep_global_registration import DeepGlobalRegistration
     from deepglobalregistration_amd.eval.formats import load_cloud
+    from deepglobalregistration_amd.core.correspondence import find_correct_correspondence
+    from deepglobalregistration_amd.eval.metrics import validation_statistics
     from deepglobalregistration_amd.model import me_conventions as mc
+    from deepglobalregistration_amd.util.pointcloud import get_matching_indices
+    T_gt = None
+    if args.gt:
+        T_gt = np.loadtxt(args.gt, dtype=np.float64)
+        if T_gt.shape != (4, 4) or not np.isfinite(T_gt).all():
+            ap.error('--gt must hold a finite 4x4 matrix')
     if args.synthetic:
         xyz0, xyz1, _ = synth.synth_pair(0, 20000)
         weights = synth.synth_checkpoint(0)
@@ -55,14 +70,25 @@ def main():
         rows.append({'kernel_order': order, 'transposed_mirrored': mirrored, 'status': dgr.last_status,
                      'wsum': wsum, 'gate': thr, 'confident_share': float((w > 0.5).float().mean()),
                      'matches_within_2_voxels_of_T': int((resid < 2 * dgr.voxel_size).sum()), 'matches': len(resid)})
+        if T_gt is not None:
+            pos = get_matching_indices(p0, p1, T_gt, 2 * dgr.voxel_size)
+            pred = torch.stack((torch.arange(len(p0), device=p0.device), dgr.last_corres_idx1.reshape(-1)), 1)
+            label = find_correct_correspondence([pos], [pred], len_batch=[[len(p0), len(p1)]])
+            counts = ops.validation_counts(torch.from_numpy(label).to(p0.device), w, [0, len(w)])
+            rows[-1].update(validation_statistics(counts))
         del dgr
         torch.cuda.empty_cache()
-    print(f"{'kernel offsets':22s} {'transposed':10s} {'status':10s} {'wsum / gate':>18s} {'w > 0.5':>8s} {'matches consistent with T':>26s}")
+    print(f"{'kernel offsets':22s} {'transposed':10s} {'status':10s} {'wsum / gate':>18s} {'w > 0.5':>8s} {'matches consistent with T':>26s}"
+          + (f" {'hit ratio':>10s} {'precision':>10s} {'recall':>10s}" if T_gt is not None else ''))
     for r in rows:
         print(f"{r['kernel_order']:22s} {'mirrored' if r['transposed_mirrored'] else 'same':10s} {r['status']:10s} "
-              f"{r['wsum']:9.1f} / {r['gate']:6.1f} {r['confident_share']:8.3f} {r['matches_within_2_voxels_of_T']:12d} / {r['matches']}")
-    best = max(rows, key=lambda r: (r['matches_within_2_voxels_of_T'], r['wsum']))
-    print(f"\nmost consistent: me_kernel_order = {best['kernel_order']!r}, me_transposed_mirrored = {best['transposed_mirrored']}"
+              f"{r['wsum']:9.1f} / {r['gate']:6.1f} {r['confident_share']:8.3f} {r['matches_within_2_voxels_of_T']:12d} / {r['matches']}"
+              + (f" {r['hit_ratio']:10.4f} {r['precision']:10.4f} {r['recall']:10.4f}" if T_gt is not None else ''))
+    if T_gt is not None:
+        best = max(rows, key=lambda r: (r['hit_ratio'], r['wsum']))
+    else:
+        best = max(rows, key=lambda r: (r['matches_within_2_voxels_of_T'], r['wsum']))
+    print(f"\n{'best hit ratio' if T_gt is not None else 'most consistent'}: me_kernel_order = {best['kernel_order']!r}, me_transposed_mirrored = {best['transposed_mirrored']}"
           + ('   (synthetic weights: no reading can stand out; this run only exercises the tool)' if args.synthetic else ''))
 
 
