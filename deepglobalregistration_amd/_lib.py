@@ -75,6 +75,8 @@ SIGNATURES = {
                                  c_f32p, c_f32p, c_i32p, c_f32p, c_i32p, vp]),
     'dgr_register_batch': (C.c_int, [vp, vp, vp, vp, vp, c_i64p, vp, vp, c_i64p, C.c_int,
                                      C.POINTER(Params), vp, vp, c_f32p, c_i32p, c_f32p, vp]),
+    'dgr_register_pairs': (C.c_int, [vp, vp, vp, vp, vp, c_i64p, C.c_int, C.c_int, c_i32p, C.c_int,
+                                     C.POINTER(Params), vp, vp, c_f32p, c_i32p, c_f32p, vp]),
     'dgr_register_batch_f64': (C.c_int, [vp, c_f64p, C.c_int64, c_i64p]),
     'dgr_register_batch_output': (C.c_int, [vp, C.c_int, vp, C.c_int64, c_i64p, vp]),
     'dgr_ctx_set_profiling': (C.c_int, [vp, C.c_int]),
@@ -126,14 +128,23 @@ class DgrError(RuntimeError):
         self.code = code
 
 
+class DgrInvalidArgument(DgrError, ValueError):
+    """DGR_EINVAL: the library refused an argument before doing any work.  A ValueError with the message it has always
+    had, and a DgrError like every other failure the library reports (`code` = DGR_EINVAL)."""
+
+    def __init__(self, message):
+        RuntimeError.__init__(self, f'libdgr_hip: {message}')
+        self.code = DGR_EINVAL
+
+
 def check(rc):
-    """0 -> ok; DGR_EINVAL -> ValueError; everything else -> RuntimeError (so that the
-    `except RuntimeError` around the SVD at core/deep_global_registration.py:295 keeps working)."""
+    """0 -> ok; DGR_EINVAL -> DgrInvalidArgument (a ValueError); everything else -> DgrError, a RuntimeError (so that
+    the `except RuntimeError` around the SVD at core/deep_global_registration.py:295 keeps working)."""
     if rc == DGR_OK:
         return
     msg = load().dgr_last_error().decode('utf-8', 'replace')
     if rc == DGR_EINVAL:
-        raise ValueError(f'libdgr_hip: {msg}')
+        raise DgrInvalidArgument(msg)
     raise DgrError(rc, msg)
 
 

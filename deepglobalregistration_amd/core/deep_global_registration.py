@@ -301,6 +301,75 @@ class DeepGlobalRegistration:
         T = T.astype(np.float64)   # (already float64 when the safeguard / ICP stages ran: their results at full width)
         return T, status, stats
 
+    # ---- a scene: every fragment featurised once, any list of pairs registered from that (no reference counterpart) --
+    def extract_fragments(self, clouds, chunk_rows=300_000):
+        """Voxelises every cloud and runs the FCGF net over them in chunks: `FragmentBank` with fragment i = clouds[i].
+        Each cloud is `preprocess`ed with its position in the chunk as the batch index and a chunk goes through
+        `fcgf_model` as ONE sparse tensor of ones; a chunk closes before the cloud that would push it past `chunk_rows`
+        voxels (a cloud larger than that is a chunk of its own).  The default is about the row count of the timed 6-pair
+        batch (12 fragments); it has not been tuned.  The bank's batch column is 0 whatever the chunking.
+        `feat_timer` covers the call."""
+        from .fragment_bank import FragmentBank
+        clouds = list(clouds)
+        if not clouds:
+            raise ValueError('no clouds')
+        self.feat_timer.tic()
+        xyz, coords, feats, off = [], [], [], [0]
+        chunk = []          # coords of the open chunk, batch column = position in the chunk
+
+        def close():
+            if chunk:
+                c = torch.cat(chunk)
+                feats.append(self.fcgf_feature_extraction(torch.ones(len(c), 1, device=self.device), c))
+                chunk.clear()
+        for cloud in clouds:
+            x, c, _ = self.preprocess(cloud, batch_index=len(chunk))
+            if len(x) == 0:
+                raise ValueError(f'cloud {len(xyz)} has no points')
+            if chunk and sum(len(k) for k in chunk) + len(c) > chunk_rows:
+                close()
+                c[:, 0] = 0     # first of the next chunk
+            chunk.append(c)
+            coords.append(c)
+            xyz.append(x)
+            off.append(off[-1] + len(x))
+        close()
+        bank_coords = torch.cat(coords)
+        bank_coords[:, 0] = 0
+        self.feat_timer.toc()
+        return FragmentBank.from_tensors(bank_coords, torch.cat(xyz), torch.cat(feats), np.asarray(off, np.int64))
+
+    def register_pairs(self, bank, pairs, batch_pairs=6, safeguard=False, icp=False, skip_refinement=False,
+                       forced_logits=None, override_idx1=None):
+        """Registers `pairs` ([n,2] integers: fragment i of `bank` onto fragment j) through the fused path
+        (`dgr_register_pairs`), `batch_pairs` consecutive pairs per library call, without voxelising or featurising
+        anything again.  Returns what `register_voxelized` returns, in the order of `pairs`; `safeguard` / `icp` /
+        `skip_refinement` as there.  A fragment may occur in any number of pairs, on either side.
+        The two harness hooks are lists with one entry per PAIR: forced_logits[k] one value per row of pair k's
+        fragment 0, override_idx1[k] rows of pair k's fragment 1 (-1 = keep the match)."""
+        from .fragment_bank import group_hooks, pair_groups
+        bd = torch.device(bank.device)    # ('cuda' without an index is the current device: not told apart here)
+        if bd.type != self.device.type or (None not in (bd.index, self.device.index) and bd.index != self.device.index):
+            raise ValueError(f'the bank is on {bank.device}, this object on {self.device}')
+        if bank.n_out != self.fcgf_model.out_channels:
+            raise ValueError(f'the bank holds {bank.n_out}-wide features, the FCGF model writes '
+                             f'{self.fcgf_model.out_channels}')
+        groups = pair_groups(bank, pairs, batch_pairs)
+        for name, seq in (('forced_logits', forced_logits), ('override_idx1', override_idx1)):
+            if seq is not None and len(seq) != sum(len(ids) for _, ids in groups):
+                raise ValueError(f'{name} must have one entry per pair')
+        out = []
+        for first, ids in groups:
+            fl, ov = group_hooks(bank, first, ids, forced_logits, override_idx1, self.device)
+            out.append(ops.register_pairs(
+                self.inlier_model._handle(), bank.coords, bank.xyz, bank.F, bank.off, ids, self.voxel_size,
+                clip_weight_thresh=self.clip_weight_thresh, inlier_feature_type=self.inlier_feature_type,
+                break_threshold_ratio=1e-4, skip_refinement=skip_refinement, forced_logit=fl, override_idx1=ov,
+                safeguard=safeguard, use_icp=icp, ransac_hypotheses=self.ransac_max_iteration,
+                ransac_seed=self.ransac_seed))
+        T, status, stats = (np.concatenate([o[k] for o in out]) for k in range(3))
+        return T.astype(np.float64), status, stats
+
     # ---- measurement beside the registration path (core/trainer.py:353-489, `_valid_epoch`) ----------------------
     def validate_collated(self, input_dict, matching_radius=None, success_rte_thresh=0.3, success_rre_thresh=15.0, **kw):
         """The validation statistics of the reference's trainer for one collated batch (layout of `register_collated`) that

@@ -310,6 +310,7 @@ struct dgr_ctx {
   hipEvent_t wait_ev = nullptr; // the event dgr_ctx_wait polls (created on first use)
   long last_wait_ns = 0;        // how long the last dgr_ctx_wait of this context took
   double batch_ns_per_row = 0;  // dgr_register_batch: the previous call's wait per input row (predicts the next call's)
+  double pairs_ns_per_row = 0;  // dgr_register_pairs: the same, learned apart (no FCGF stage: fewer ns per row)
   // pinned host landing buffer of the small device-to-host copies that end a call (error flag word at offset 0, result
   // records from offset 64): a copy into PINNED memory is asynchronous, so it is enqueued BEFORE the call's one wait
   // (dgr_ctx_wait) instead of blocking inside the runtime after it (a pageable copy + hipStreamSynchronize: ~100 us each)

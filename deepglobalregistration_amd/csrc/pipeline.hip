@@ -156,6 +156,34 @@ struct StageTimer {
   }
 };
 
+// the buffers of a batch behind its features, in the order dgr_register_batch has always taken them from the arena
+struct BatchBuffers {
+  int64_t *idx1, *off0_dev;
+  int32_t *coords6;
+  float *feats6, *logit, *weights;
+  DgrRegResult *res_dev;
+};
+
+static int alloc_batch_buffers(DgrArena &A, int64_t n0, int npairs, const int64_t *off0, hipStream_t stream,
+                               BatchBuffers *B) {
+  DGR_ALLOC(B->idx1, A, int64_t, n0);
+  DGR_ALLOC(B->coords6, A, int32_t, n0 * 7);
+  DGR_ALLOC(B->feats6, A, float, n0 * 6);
+  DGR_ALLOC(B->logit, A, float, n0);
+  DGR_ALLOC(B->weights, A, float, n0);
+  DGR_ALLOC(B->off0_dev, A, int64_t, npairs + 1);
+  DGR_ALLOC(B->res_dev, A, DgrRegResult, npairs);
+  DGR_HIP_CHECK(hipMemcpyAsync(B->off0_dev, off0, (size_t)(npairs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+  return DGR_OK;
+}
+
+static int register_from_features(dgr_ctx *ctx, dgr_net *inlier, const int32_t *coords0, const float *xyz0,
+                                  const int64_t *off0, const int32_t *coords1, const float *xyz1, const int64_t *off1,
+                                  const float *F0, const float *F1, int C, int npairs, const dgr_params *prm,
+                                  const int64_t *override_idx1, const float *forced_logit, const BatchBuffers &B,
+                                  StageTimer &tm, double *ns_per_row, float *T_out, int32_t *status_out,
+                                  float *stats_out, hipStream_t stream);
+
 extern "C" int dgr_register_batch(dgr_ctx *ctx, dgr_net *fcgf, dgr_net *inlier, const int32_t *coords0,
                                   const float *xyz0, const int64_t *off0, const int32_t *coords1,
                                   const float *xyz1, const int64_t *off1, int npairs, const dgr_params *prm,
@@ -187,21 +215,12 @@ extern "C" int dgr_register_batch(dgr_ctx *ctx, dgr_net *fcgf, dgr_net *inlier, 
   const int C = dgr_net_out_channels(fcgf);
   StageTimer tm{ctx, stream, {}, ctx->profiling};
 
-  float *F0, *F1, *ones, *feats6, *logit, *weights;
-  int64_t *idx1, *off0_dev;
-  int32_t *coords6;
-  DgrRegResult *res_dev;
+  float *F0, *F1, *ones;
+  BatchBuffers B;
   DGR_ALLOC(F0, A, float, (n0 + n1) * C);
   F1 = F0 + n0 * C;  // one forward over both fragments writes [F0; F1]
   DGR_ALLOC(ones, A, float, n0 + n1);
-  DGR_ALLOC(idx1, A, int64_t, n0);
-  DGR_ALLOC(coords6, A, int32_t, n0 * 7);
-  DGR_ALLOC(feats6, A, float, n0 * 6);
-  DGR_ALLOC(logit, A, float, n0);
-  DGR_ALLOC(weights, A, float, n0);
-  DGR_ALLOC(off0_dev, A, int64_t, npairs + 1);
-  DGR_ALLOC(res_dev, A, DgrRegResult, npairs);
-  DGR_HIP_CHECK(hipMemcpyAsync(off0_dev, off0, (size_t)(npairs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+  DGR_CHECK(alloc_batch_buffers(A, n0, npairs, off0, stream, &B));
   fill_kernel<<<256, 256, 0, stream>>>(ones, n0 + n1, 1.f);
 
   // Step 1: FCGF features of both fragments (feats = ones[N,1], :160)
@@ -218,6 +237,27 @@ extern "C" int dgr_register_batch(dgr_ctx *ctx, dgr_net *fcgf, dgr_net *inlier, 
     dgr_net_invalidate_runs(fcgf);
   }
   DGR_CHECK(tm.rec(0, 1));
+  return register_from_features(ctx, inlier, coords0, xyz0, off0, coords1, xyz1, off1, F0, F1, C, npairs, prm,
+                                override_idx1, forced_logit, B, tm, &ctx->batch_ns_per_row, T_out, status_out, stats_out,
+                                stream);
+}
+
+// Steps 2 to 5 and the Open3D tail of a batch whose features F0 / F1 [sum N, C] are on the device: the part that
+// dgr_register_batch (features from the FCGF net) and dgr_register_pairs (features from the caller's bank) share.
+// `ns_per_row`: the calling entry point's own wait predictor.
+static int register_from_features(dgr_ctx *ctx, dgr_net *inlier, const int32_t *coords0, const float *xyz0,
+                                  const int64_t *off0, const int32_t *coords1, const float *xyz1, const int64_t *off1,
+                                  const float *F0, const float *F1, int C, int npairs, const dgr_params *prm,
+                                  const int64_t *override_idx1, const float *forced_logit, const BatchBuffers &B,
+                                  StageTimer &tm, double *ns_per_row, float *T_out, int32_t *status_out,
+                                  float *stats_out, hipStream_t stream) {
+  DgrArena &A = ctx->arena;
+  const int64_t n0 = off0[npairs], n1 = off1[npairs];
+  const int ftype = prm->inlier_feature_type;
+  int64_t *const idx1 = B.idx1, *const off0_dev = B.off0_dev;
+  int32_t *const coords6 = B.coords6;
+  float *const feats6 = B.feats6, *const logit = B.logit, *const weights = B.weights;
+  DgrRegResult *const res_dev = B.res_dev;
   // Step 2: coarse correspondences, per pair (corres_idx0 = arange)
   DGR_CHECK(tm.rec(1, 0));
   // one launch per kernel for all pairs; the indices come out as rows of the concatenated F1
@@ -257,8 +297,8 @@ extern "C" int dgr_register_batch(dgr_ctx *ctx, dgr_net *fcgf, dgr_net *inlier, 
   const DgrRegResult *res = reinterpret_cast<const DgrRegResult *>(pin + 64);
   DGR_HIP_CHECK(hipMemcpyAsync(pin + 64, res_dev, (size_t)npairs * sizeof(DgrRegResult), hipMemcpyDeviceToHost, stream));
   DGR_HIP_CHECK(hipMemcpyAsync(pin, ctx->flag_dev, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  DGR_CHECK(dgr_ctx_wait(ctx, stream, (long)(ctx->batch_ns_per_row * (double)(n0 + n1))));
-  ctx->batch_ns_per_row = (double)ctx->last_wait_ns / (double)(n0 + n1);
+  DGR_CHECK(dgr_ctx_wait(ctx, stream, (long)(*ns_per_row * (double)(n0 + n1))));
+  *ns_per_row = (double)ctx->last_wait_ns / (double)(n0 + n1);
   DGR_CHECK(dgr_flag_error(*reinterpret_cast<volatile int32_t *>(pin)));
   for (int p = 0; p < npairs; ++p)
     if (res[p].status == DGR_STATUS_EXCHANGE_TIMEOUT) {
@@ -375,6 +415,137 @@ extern "C" int dgr_register_batch(dgr_ctx *ctx, dgr_net *fcgf, dgr_net *inlier, 
     DGR_CHECK(dgr_ctx_collect_profile(ctx));
   }
   return DGR_OK;
+}
+
+// ---- pairs of a fragment bank (dgr_register_pairs) -----------------------------------------------------
+// One segment = one side of one pair: `count` rows of the bank from row `src` on become rows `dst` .. of the batch's
+// concatenation [fragment-0 rows of all pairs; fragment-1 rows of all pairs].  The table is ascending in dst and tiles
+// [0, total) without gaps (built on the host from validated offsets), which is what bounds every access below.
+struct BankSegment {
+  int64_t src, dst, count;
+  int32_t pair, side;
+};
+constexpr int BANK_GATHER_ROWS = 256;   // destination rows per workgroup (= its thread count)
+
+// Memory-bound row copy, every access 16-byte wide or lane-contiguous: coords as one int4 per row (batch column := pair),
+// xyz and F as flat runs of the block's 256 destination rows, so that consecutive lanes write consecutive addresses
+// (and, inside a segment, read consecutive ones).  A block overlaps at most 256 segments: it finds its first one in the
+// global table, keeps that window in LDS, and each row searches the window.
+__global__ __launch_bounds__(BANK_GATHER_ROWS) void bank_gather_kernel(
+    const int4 *__restrict__ bank_coords, const float *__restrict__ bank_xyz, const float4 *__restrict__ bank_F,
+    const BankSegment *__restrict__ segs, int nseg, int64_t total, int c4_shift, int4 *__restrict__ coords,
+    float *__restrict__ xyz, float4 *__restrict__ F) {
+  __shared__ BankSegment s_seg[BANK_GATHER_ROWS];
+  __shared__ int64_t s_src[BANK_GATHER_ROWS];
+  const int t = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * BANK_GATHER_ROWS;
+  const int rows = (int)(total - r0 < BANK_GATHER_ROWS ? total - r0 : BANK_GATHER_ROWS);
+  int lo = 0, hi = nseg - 1;   // the last segment that starts at or before r0 (segs[0].dst == 0)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (segs[mid].dst <= r0) lo = mid; else hi = mid - 1;
+  }
+  const int first = lo;
+  // segments are not empty, so at most `rows` of them start inside the block: a prefix of first .. first + 255
+  const bool mine = first + t < nseg && (t == 0 || segs[first + t].dst < r0 + rows);
+  if (mine) s_seg[t] = segs[first + t];
+  const int ns = __syncthreads_count(mine);
+  if (t < rows) {
+    const int64_t r = r0 + t;
+    int a = 0, b = ns - 1;
+    while (a < b) {
+      const int mid = (a + b + 1) >> 1;
+      if (s_seg[mid].dst <= r) a = mid; else b = mid - 1;
+    }
+    const int64_t src = s_seg[a].src + (r - s_seg[a].dst);
+    s_src[t] = src;
+    int4 c = bank_coords[src];
+    c.x = s_seg[a].pair;
+    coords[r] = c;
+  }
+  __syncthreads();
+  for (int f = t; f < rows * 3; f += BANK_GATHER_ROWS) {
+    const int row = f / 3;
+    xyz[r0 * 3 + f] = bank_xyz[s_src[row] * 3 + (f - row * 3)];
+  }
+  const int c4 = 1 << c4_shift;   // 16-byte pieces per feature row
+#pragma unroll 4
+  for (int q = t; q < (rows << c4_shift); q += BANK_GATHER_ROWS)
+    F[(r0 << c4_shift) + q] = bank_F[(s_src[q >> c4_shift] << c4_shift) + (q & (c4 - 1))];
+}
+
+extern "C" int dgr_register_pairs(dgr_ctx *ctx, dgr_net *inlier, const int32_t *bank_coords, const float *bank_xyz,
+                                  const float *bank_F, const int64_t *bank_off, int nfrag, int C,
+                                  const int32_t *pair_ids, int npairs, const dgr_params *prm,
+                                  const int64_t *override_idx1, const float *forced_logit, float *T_out,
+                                  int32_t *status_out, float *stats_out, dgr_stream stream_) {
+  DGR_REQUIRE(ctx && inlier && bank_coords && bank_xyz && bank_F && bank_off && pair_ids && prm && T_out && status_out,
+              "dgr_register_pairs: NULL argument");
+  DGR_REQUIRE(npairs >= 1 && npairs <= 65535, "dgr_register_pairs: npairs=%d out of range", npairs);
+  DGR_REQUIRE(nfrag >= 1, "dgr_register_pairs: nfrag=%d", nfrag);
+  DGR_REQUIRE(C == 16 || C == 32 || C == 64, "dgr_register_pairs: feature width %d not supported (16, 32, 64)", C);
+  DGR_REQUIRE(((uintptr_t)bank_coords & 15) == 0 && ((uintptr_t)bank_F & 15) == 0,
+              "dgr_register_pairs: bank_coords and bank_F must be 16-byte aligned");
+  DGR_REQUIRE(dgr_net_dim(inlier) == 6, "dgr_register_pairs: expects the 6-D inlier net");
+  const int ftype = prm->inlier_feature_type;
+  DGR_REQUIRE((ftype == 0 && dgr_net_in_channels(inlier) == 1) || (ftype == 1 && dgr_net_in_channels(inlier) == 6),
+              "inlier_feature_type %d does not match the inlier network input width %d", ftype,
+              dgr_net_in_channels(inlier));
+  DGR_REQUIRE(dgr_net_ctx(inlier) == ctx,
+              "dgr_register_pairs: the net object belongs to another context (one dgr_net per context: dgr_net_share)");
+  DGR_REQUIRE(bank_off[0] >= 0, "dgr_register_pairs: bank_off[0] = %lld", (long long)bank_off[0]);
+  for (int f = 0; f < nfrag; ++f)
+    DGR_REQUIRE(bank_off[f + 1] > bank_off[f], "fragment %d of the bank is empty", f);
+  // the segment table (fragment-0 sides first: dst ascending) and the offsets of the batch layout
+  std::vector<BankSegment> segs((size_t)2 * npairs);
+  std::vector<int64_t> off0(npairs + 1, 0), off1(npairs + 1, 0);
+  for (int s = 0; s < 2; ++s) {
+    std::vector<int64_t> &off = s ? off1 : off0;
+    for (int p = 0; p < npairs; ++p) {
+      const int32_t f = pair_ids[2 * p + s];
+      DGR_REQUIRE(f >= 0 && f < nfrag, "pair %d: fragment id %d outside [0, %d)", p, f, nfrag);
+      off[p + 1] = off[p] + (bank_off[f + 1] - bank_off[f]);
+      segs[(size_t)s * npairs + p] = {bank_off[f], off[p], bank_off[f + 1] - bank_off[f], p, s};
+    }
+  }
+  const int64_t n0 = off0[npairs], n1 = off1[npairs];
+  for (int p = 0; p < npairs; ++p) segs[(size_t)npairs + p].dst += n0;
+  hipStream_t stream = (hipStream_t)stream_;
+  DGR_HIP_CHECK(hipSetDevice(ctx->device));
+  ctx->last_T64.clear();
+  DGR_CHECK(ctx->arena.reset());
+  dgr_ctx_begin_profile(ctx);
+  DGR_CHECK(dgr_ctx_new_flag(ctx, stream));
+  DgrArena &A = ctx->arena;
+  StageTimer tm{ctx, stream, {}, ctx->profiling};
+
+  int32_t *coords;
+  float *xyz, *F0;
+  BankSegment *segs_dev;
+  BatchBuffers B;
+  DGR_ALLOC(F0, A, float, (n0 + n1) * C);   // [F0; F1] adjacent, as the FCGF forward of dgr_register_batch leaves them
+  DGR_ALLOC(coords, A, int32_t, (n0 + n1) * 4);
+  DGR_ALLOC(xyz, A, float, (n0 + n1) * 3);
+  DGR_ALLOC(segs_dev, A, BankSegment, segs.size());
+  // `segs`, `off0` and `off1` are read by asynchronous copies and by the shared tail: they live until this function
+  // returns, and it does not return before the stream is idle
+  auto run = [&]() -> int {
+    DGR_CHECK(alloc_batch_buffers(A, n0, npairs, off0.data(), stream, &B));
+    DGR_CHECK(tm.rec(0, 0));
+    DGR_HIP_CHECK(hipMemcpyAsync(segs_dev, segs.data(), segs.size() * sizeof(BankSegment), hipMemcpyHostToDevice, stream));
+    bank_gather_kernel<<<(int)dgr_ceil_div(n0 + n1, BANK_GATHER_ROWS), BANK_GATHER_ROWS, 0, stream>>>(
+        reinterpret_cast<const int4 *>(bank_coords), bank_xyz, reinterpret_cast<const float4 *>(bank_F), segs_dev,
+        2 * npairs, n0 + n1, C == 16 ? 2 : C == 32 ? 3 : 4, reinterpret_cast<int4 *>(coords), xyz,
+        reinterpret_cast<float4 *>(F0));
+    DGR_LAUNCH_CHECK();
+    DGR_CHECK(tm.rec(0, 1));
+    return register_from_features(ctx, inlier, coords, xyz, off0.data(), coords + n0 * 4, xyz + n0 * 3, off1.data(), F0,
+                                  F0 + n0 * C, C, npairs, prm, override_idx1, forced_logit, B, tm, &ctx->pairs_ns_per_row,
+                                  T_out, status_out, stats_out, stream);
+  };
+  const int rc = run();
+  if (rc != DGR_OK) (void)hipStreamSynchronize(stream);   // (the success path has waited already)
+  return rc;
 }
 
 extern "C" int dgr_register_batch_f64(dgr_ctx *ctx, double *T_out, int64_t capacity_pairs, int64_t *npairs) {

@@ -8,7 +8,7 @@ import argparse
 import numpy as np
 import torch
 
-from . import KITTIOdometryPairs, ThreeDMatchTrajectory, evaluate, evaluate_kitti
+from . import KITTIOdometryPairs, ThreeDMatchTrajectory, evaluate, evaluate_batched, evaluate_kitti
 
 
 def main():
@@ -22,6 +22,9 @@ def main():
     ap.add_argument('--success_rte_thresh', type=float, default=0.3)
     ap.add_argument('--success_rre_thresh', type=float, default=15.0)
     ap.add_argument('--no_icp', action='store_true')
+    ap.add_argument('--batched', action='store_true',
+                    help='3DMatch: featurise every fragment of a scene once and register its records in fused batches')
+    ap.add_argument('--batch_pairs', type=int, default=6, help='pairs per fused call with --batched')
     ap.add_argument('--out', default='3dmatch-stats_DeepGlobalRegistration.npz')
     args = ap.parse_args()
     from ..core.deep_global_registration import DeepGlobalRegistration
@@ -45,8 +48,12 @@ def main():
     if not args.threed_match_dir:
         ap.error('--threed_match_dir or --kitti_dir is required')
     ds = ThreeDMatchTrajectory(args.threed_match_dir, args.scenes)
-    stats, scene_means, _ = evaluate([dgr], ['DGR'], ds, args.success_rte_thresh, args.success_rre_thresh,
-                                     summary_every=10)
+    if args.batched:
+        stats, scene_means, _ = evaluate_batched(dgr, ds, args.success_rte_thresh, args.success_rre_thresh,
+                                                 batch_pairs=args.batch_pairs)
+    else:
+        stats, scene_means, _ = evaluate([dgr], ['DGR'], ds, args.success_rte_thresh, args.success_rre_thresh,
+                                         summary_every=10)
     np.savez(args.out, stats=stats, names=['DGR'], scenes=ds.scenes, scene_means=scene_means)
     print('scene-wise mean [success, RTE, RRE]:')
     for s, v in zip(ds.scenes, scene_means[0]):

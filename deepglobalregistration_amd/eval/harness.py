@@ -35,6 +35,14 @@ class ThreeDMatchTrajectory:
         return (s, load_cloud(os.path.join(self.root, s, f'cloud_bin_{i}.ply')),
                 load_cloud(os.path.join(self.root, s, f'cloud_bin_{j}.ply')), T)
 
+    def fragment(self, scene, i):
+        """The cloud of fragment i of `scene`."""
+        return load_cloud(os.path.join(self.root, scene, f'cloud_bin_{i}.ply'))
+
+    def records(self, scene):
+        """The (i, j, pose) triples of `scene` in file order (the order its items have in the dataset)."""
+        return [(i, j, T) for s, i, j, T in self.files if s == scene]
+
 
 def analyze_stats(stats, mask, method_names, out=print):
     """Mean [success, RTE, RRE, time, scene id] over the evaluated pairs, and over the successful ones."""
@@ -82,4 +90,45 @@ def evaluate(methods, method_names, dataset, success_rte_thresh=0.3, success_rre
             sel = stats[m, :, 4] == sid
             if sel.any():
                 scene_means[m, sid] = stats[m, sel, :3].mean(0)
+    return stats, scene_means, summary
+
+
+def evaluate_batched(method, dataset, success_rte_thresh=0.3, success_rre_thresh=15.0, batch_pairs=6, out=print):
+    """`evaluate` for one method that can register a scene's pair list from features computed once per fragment:
+    per scene, every fragment that occurs in a record is loaded once, `method.extract_fragments(clouds)` featurises
+    them, and `method.register_pairs(bank, pairs, batch_pairs, safeguard=True, icp=method.use_icp)` registers all
+    records (the flags give the branch structure of `register()`: gate, safeguard RANSAC, final ICP).  Metrics as in
+    `evaluate` (T_gt = inv(pose)); returns the same (stats [1, pairs, 5], per-scene means [1, scenes, 3], summary).
+    The time column is NOT the per-call time `evaluate` records: it is the scene's wall time, from the first load to a
+    device synchronisation behind the last batch, divided by the scene's records."""
+    scenes = list(dataset.scenes)
+    stats = np.zeros((1, len(dataset), 5))
+    k = 0
+    for sid, sname in enumerate(scenes):      # (dataset.files lists the scenes in this order)
+        recs = dataset.records(sname)
+        if not recs:
+            continue
+        t0 = time.time()
+        frags = sorted({f for i, j, _ in recs for f in (i, j)})
+        slot = {f: n for n, f in enumerate(frags)}
+        bank = method.extract_fragments([dataset.fragment(sname, f) for f in frags])
+        T, _, _ = method.register_pairs(bank, [(slot[i], slot[j]) for i, j, _ in recs], batch_pairs,
+                                        safeguard=True, icp=method.use_icp)
+        dev = getattr(method, 'device', None)
+        if dev is not None and getattr(dev, 'type', None) == 'cuda':
+            import torch
+            torch.cuda.synchronize(dev)
+        dt = (time.time() - t0) / len(recs)
+        for r, (_, _, pose) in enumerate(recs):
+            stats[0, k, :3] = rte_rre(T[r], np.linalg.inv(pose), success_rte_thresh, success_rre_thresh)
+            stats[0, k, 3] = dt
+            stats[0, k, 4] = sid
+            k += 1
+    assert k == len(dataset)
+    summary = analyze_stats(stats, np.ones((len(dataset), 1), int), ['DGR'], out)
+    scene_means = np.zeros((1, len(scenes), 3))
+    for sid in range(len(scenes)):
+        sel = stats[0, :, 4] == sid
+        if sel.any():
+            scene_means[0, sid] = stats[0, sel, :3].mean(0)
     return stats, scene_means, summary

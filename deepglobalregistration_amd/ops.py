@@ -627,6 +627,61 @@ def register_batch(fcgf, inlier, coords0, xyz0, off0, coords1, xyz1, off1, voxel
     return T64.reshape(npairs, 4, 4), status, stats
 
 
+def register_pairs(inlier, bank_coords, bank_xyz, bank_F, bank_off, pair_ids, voxel_size,
+                   clip_weight_thresh=0.05, inlier_feature_type='coords', max_iter=1000,
+                   max_break_count=20, break_threshold_ratio=1e-4, skip_refinement=False,
+                   forced_logit=None, override_idx1=None, safeguard=False, use_icp=False, ransac_hypotheses=4000000,
+                   ransac_seed=0):
+    """`register_batch` for pairs of fragments whose FCGF features exist already (dgr_register_pairs): the bank is
+    coords int32 [N,4], xyz f32 [N,3], F f32 [N,C] on the device of `inlier` with fragment f in rows
+    bank_off[f]:bank_off[f+1] (host, [nfrag+1]); pair_ids is [npairs,2] (fragment 0, fragment 1).  The library copies the
+    rows into the batch layout and runs the stages behind the FCGF net; `forced_logit` (one value per row of the pairs'
+    concatenated fragment 0) and `override_idx1` (rows of the concatenated fragment 1) mean what they mean there.
+    Returns T [npairs,4,4] float64, status [npairs] int32, stats [npairs,4] float32, as `register_batch` does."""
+    lib = _lib.load()
+    dev = inlier.device
+    off = np.ascontiguousarray(np.asarray(bank_off), dtype=np.int64).reshape(-1)
+    ids = np.ascontiguousarray(np.asarray(pair_ids), dtype=np.int32)
+    if ids.ndim != 2 or ids.shape[1] != 2:
+        raise ValueError('pair_ids must be [npairs,2]')
+    npairs, nfrag = len(ids), len(off) - 1
+    bank_coords, bank_xyz = _as(bank_coords, torch.int32, dev), _as(bank_xyz, torch.float32, dev)
+    bank_F = _as(bank_F, torch.float32, dev)
+    if nfrag < 1 or bank_coords.shape[0] != off[-1] or bank_xyz.shape[0] != off[-1] or bank_F.shape[0] != off[-1] \
+            or bank_F.dim() != 2:
+        raise ValueError('offset array does not match the bank arrays')
+    prm = _lib.Params(float(clip_weight_thresh), float(voxel_size),
+                      {'ones': 0, 'coords': 1}[inlier_feature_type], int(max_iter), int(max_break_count),
+                      float(break_threshold_ratio), int(bool(skip_refinement)), int(bool(safeguard)),
+                      int(ransac_hypotheses), int(ransac_seed) & 0xffffffff, int(bool(use_icp)))
+    T = np.empty((npairs, 16), np.float32)
+    status = np.empty(npairs, np.int32)
+    stats = np.empty((npairs, 4), np.float32)
+    in_range = bool(((ids >= 0) & (ids < nfrag)).all())      # (out-of-range ids are the library's to report)
+    n0 = int((off[ids[:, 0] + 1] - off[ids[:, 0]]).sum()) if in_range else -1
+    fl = None
+    if forced_logit is not None:
+        fl = _as(forced_logit, torch.float32, dev).reshape(-1)
+        if in_range and fl.shape[0] != n0:
+            raise ValueError('forced_logit must have one entry per row of fragment 0')
+    ov = None
+    if override_idx1 is not None:
+        ov = _as(override_idx1, torch.int64, dev).reshape(-1)
+        if in_range and ov.shape[0] != n0:
+            raise ValueError('override_idx1 must have one entry per row of fragment 0')
+    check(lib.dgr_register_pairs(get_ctx(dev), inlier.handle, ptr(bank_coords), ptr(bank_xyz), ptr(bank_F),
+                                 off.ctypes.data_as(_lib.c_i64p), nfrag, int(bank_F.shape[1]),
+                                 ids.ctypes.data_as(_lib.c_i32p), npairs, C.byref(prm), ptr(ov), ptr(fl),
+                                 T.ctypes.data_as(_lib.c_f32p), status.ctypes.data_as(_lib.c_i32p),
+                                 stats.ctypes.data_as(_lib.c_f32p), stream_ptr(dev.index)))
+    T64 = np.empty((npairs, 16), np.float64)   # (see register_batch)
+    n = C.c_int64(0)
+    check(lib.dgr_register_batch_f64(get_ctx(dev), T64.ctypes.data_as(_lib.c_f64p), npairs, C.byref(n)))
+    if n.value != npairs:
+        raise RuntimeError(f'dgr_register_batch_f64 holds {n.value} pairs, expected {npairs}')
+    return T64.reshape(npairs, 4, 4), status, stats
+
+
 _BATCH_OUT = {'idx1': (0, torch.int64), 'logit': (1, torch.float32), 'weights': (2, torch.float32),
               'F0': (3, torch.float32), 'F1': (4, torch.float32)}
 

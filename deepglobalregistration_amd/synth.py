@@ -125,6 +125,32 @@ def synth_pair(seed, n_raw=50000, kind='indoor', max_angle_deg=180.0, grid_align
     return np.ascontiguousarray(v0), np.ascontiguousarray(v1), T
 
 
+def synth_scene(seed, n_fragments, n_raw=50000, window=0.55, min_overlap=0.5, max_angle_deg=180.0):
+    """A scene as a scan sequence sees it: `n_fragments` windows of ONE `_indoor_scene` room, each `window` of the room's
+    length wide, their centres evenly spaced along x, every fragment an own random subset of `n_raw` points of its window
+    in its own random frame.  Returns (clouds, poses, pairs): clouds[k] [n_raw,3] float64 in fragment k's frame;
+    poses [n,4,4] with x_k = poses[k] . x_world; pairs = [(i, j, T_gt), ...] for every i < j whose windows share at
+    least `min_overlap` of their width, x_j = T_gt . x_i on the overlap (what `register()` estimates for (i, j)).
+    Deterministic in `seed`."""
+    if n_fragments < 2:
+        raise ValueError('a scene needs at least two fragments')
+    rng = np.random.default_rng(seed)
+    pts, room = _indoor_scene(rng, 4 * n_raw)
+    w = window * room[0]
+    centres = np.linspace(w / 2, room[0] - w / 2, n_fragments)
+    clouds, poses = [], np.tile(np.eye(4), (n_fragments, 1, 1))
+    for k, c in enumerate(centres):
+        v = pts[np.abs(pts[:, 0] - c) <= w / 2]
+        assert len(v) >= n_raw, (len(v), n_raw)
+        v = v[rng.permutation(len(v))[:n_raw]]
+        poses[k, :3, :3] = _random_rotation(rng, max_angle_deg)
+        poses[k, :3, 3] = rng.uniform(-0.5, 0.5, size=3)
+        clouds.append(np.ascontiguousarray(v @ poses[k, :3, :3].T + poses[k, :3, 3]))
+    pairs = [(i, j, poses[j] @ np.linalg.inv(poses[i])) for i in range(n_fragments) for j in range(i + 1, n_fragments)
+             if w - (centres[j] - centres[i]) >= min_overlap * w]
+    return clouds, poses, pairs
+
+
 # ----------------------------------------------------------------------------
 # weights
 # ----------------------------------------------------------------------------

@@ -286,6 +286,21 @@ int dgr_register_batch(dgr_ctx *ctx, dgr_net *fcgf, dgr_net *inlier, const int32
                        const int64_t *override_idx1, const float *forced_logit, float *T_out,
                        int32_t *status_out,
                        float *stats_out, dgr_stream stream);
+/* The same pipeline from the second stage on, for pairs of fragments whose FCGF features are already computed: the
+ * "bank" is the caller's DEVICE memory, fragment f = rows bank_off[f] .. bank_off[f + 1] of bank_coords (int32 [N,4],
+ * 16-byte aligned), bank_xyz (f32 [N,3]) and bank_F (f32 [N,C], 16-byte aligned, C = 16 | 32 | 64); bank_off is HOST
+ * [nfrag + 1], ascending from >= 0 with no empty fragment.  pair_ids is HOST [npairs,2]: pair p registers fragment
+ * pair_ids[2p] (fragment 0) onto fragment pair_ids[2p + 1] (fragment 1).  A fragment may occur any number of times, on
+ * either side.  One kernel copies the rows into the concatenated layout dgr_register_batch takes (batch column = p);
+ * from there on the two calls run the same code.  override_idx1 / forced_logit index that concatenation, as in
+ * dgr_register_batch: rows of the concatenated fragment 1 / one value per row of the concatenated fragment 0.  The
+ * library keeps nothing of the bank.  dgr_register_batch_output / _f64 serve this call like the other (which = 3, 4:
+ * the gathered feature rows); stage time [0] is the gather. */
+int dgr_register_pairs(dgr_ctx *ctx, dgr_net *inlier, const int32_t *bank_coords, const float *bank_xyz,
+                       const float *bank_F, const int64_t *bank_off, int nfrag, int C, const int32_t *pair_ids,
+                       int npairs, const dgr_params *params, const int64_t *override_idx1,
+                       const float *forced_logit, float *T_out, int32_t *status_out, float *stats_out,
+                       dgr_stream stream);
 /* device-side intermediates of the last dgr_register_batch (valid until the next call on this
  * ctx): which = 0 idx1 (int64 [sumN0]), 1 logit (f32 [sumN0]), 2 weights (f32 [sumN0]),
  * 3 F0 (f32 [sumN0,C]), 4 F1 (f32 [sumN1,C]).  *numel receives the element count; when dst_dev is
