@@ -93,6 +93,7 @@ SIGNATURES = {
                                          C.c_int64, c_i64p, vp]),
     'dgr_pairs_isin_batch': (C.c_int, [vp, vp, c_i64p, vp, c_i64p, C.c_int, c_i64p, vp, vp]),
     'dgr_validation_counts': (C.c_int, [vp, vp, vp, C.c_float, c_i64p, C.c_int, c_i64p, vp]),
+    'dgr_score_pairs': (C.c_int, [vp, vp, c_i64p, C.c_int, c_i32p, C.c_int, c_f64p, C.c_double, c_f64p, vp]),
     'dgr_debug_ortho2rotation': (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, vp]),
     'dgr_debug_se3_refine_from': (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_double,
                                             c_f64p, c_f64p, vp]),

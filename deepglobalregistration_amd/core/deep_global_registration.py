@@ -370,6 +370,40 @@ class DeepGlobalRegistration:
         T, status, stats = (np.concatenate([o[k] for o in out]) for k in range(3))
         return T.astype(np.float64), status, stats
 
+    def score_pairs(self, bank, pairs, T, radius=None):
+        """The geometric fit of `pairs` ([n,2] integers: fragment i of `bank` onto fragment j) under the poses `T`
+        [n,4,4] (i into j's frame, e.g. what `register_pairs` returned): pair k is scored as (i, j) under T[k] and as
+        (j, i) under inv(T[k]) in ONE library call of 2n directed pairs (`dgr_score_pairs`).  `radius` defaults to 2
+        voxels, the distance the reference gives its ICP (:317-322).  Returns a dict of per-pair arrays: `n_corr`,
+        `fitness` (rows of i with a row of j strictly within the radius, over the rows of i), `inlier_rmse`,
+        `information` [n,6,6] (Open3D's order: rotation, translation; `core.pair_score`), `fitness_reverse` (the same
+        share of j's rows) and `overlap` = max(fitness, fitness_reverse) -- the reference's `compute_overlap_ratio`
+        (util/pointcloud.py:72-80) at that radius.  Only the bank's `xyz` is read: neither network runs and the feature
+        width does not matter.  The bank's device and the pair ids are checked as in `register_pairs`."""
+        from .fragment_bank import pair_groups
+        from .pair_score import scores_from_sums
+        bd = torch.device(bank.device)
+        if bd.type != self.device.type or (None not in (bd.index, self.device.index) and bd.index != self.device.index):
+            raise ValueError(f'the bank is on {bank.device}, this object on {self.device}')
+        ids = np.concatenate([g for _, g in pair_groups(bank, pairs, 1)])
+        n = len(ids)
+        radius = 2 * self.voxel_size if radius is None else radius
+        _, _, T, radius = ops.check_score_args(len(bank.xyz), bank.off, ids, T, radius)
+        T = T.reshape(n, 4, 4).copy()
+        T[:, 3] = (0, 0, 0, 1)                    # (the library ignores the last row; the inverse must not see it)
+        try:
+            T_inv = np.linalg.inv(T)
+        except np.linalg.LinAlgError as e:
+            raise ValueError(f'a pose cannot be inverted: {e}') from None
+        if not np.isfinite(T_inv).all():
+            raise ValueError('a pose cannot be inverted')
+        sums = ops.score_pairs(bank.xyz, bank.off, np.concatenate((ids, ids[:, ::-1])), np.concatenate((T, T_inv)), radius)
+        rows = np.diff(bank.off)
+        out = scores_from_sums(sums[:n], rows[ids[:, 0]])
+        out['fitness_reverse'] = scores_from_sums(sums[n:], rows[ids[:, 1]])['fitness']
+        out['overlap'] = np.maximum(out['fitness'], out['fitness_reverse'])
+        return out
+
     # ---- measurement beside the registration path (core/trainer.py:353-489, `_valid_epoch`) ----------------------
     def validate_collated(self, input_dict, matching_radius=None, success_rte_thresh=0.3, success_rre_thresh=15.0, **kw):
         """The validation statistics of the reference's trainer for one collated batch (layout of `register_collated`) that

@@ -43,3 +43,39 @@ def batch_rte_rre(R_pred, t_pred, T_gt):
     rre = np.degrees(np.arccos(np.clip(side, -0.999, 0.999)))
     rte = np.linalg.norm(t_pred - T_gt[:, :3, 3], axis=1)
     return rte, rre
+
+
+def rotation_vector(R):
+    """The rotation vector (axis times angle, angle in [0, pi]) of a 3x3 rotation matrix."""
+    R = np.asarray(R, np.float64)
+    w = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])   # sin(angle) * axis
+    s, c = float(np.linalg.norm(w)), (float(np.trace(R)) - 1.0) / 2.0
+    angle = float(np.arctan2(s, c))
+    if s > 1e-6:
+        return w * (angle / s)
+    if c > 0:                                   # angle -> 0: angle / sin(angle) -> 1
+        return w
+    # angle -> pi: the axis from the symmetric part R + R^T = 2 cos I + 2 (1 - cos) a a^T, signed by its largest entry
+    A = (R + R.T) / 2.0 - c * np.eye(3)
+    k = int(np.argmax(np.diag(A)))
+    a = A[k] / np.sqrt(max(A[k, k] * (1.0 - c), 1e-300))
+    return a / np.linalg.norm(a) * angle
+
+
+def information_rmse(T_a, T_b, info):
+    """The RMSE between the poses T_a and T_b over the correspondences that the 6x6 information matrix `info`
+    summarises (`core.pair_score.information_from_sums`; a record of a `.info` file): sqrt(xi^T info xi / info[3,3]) with
+    xi = (omega, v), omega the rotation vector of E = T_a T_b^-1 and v its translation; info[3,3] is the number of
+    correspondences, `inf` when it is 0.  To first order in the rotation, xi^T info xi = sum |E q - q|^2 over the
+    correspondences' target points q.  The 3DMatch / Redwood benchmark thresholds the same quantity (0.2 m) in its
+    Matlab evaluation, which is not available here: the formula is derived from the definition of the information matrix,
+    not copied from that code."""
+    info = np.asarray(info, np.float64)
+    if info.shape != (6, 6):
+        raise ValueError(f'info must be [6,6], got {info.shape}')
+    n = info[3, 3]
+    if not n > 0:
+        return float('inf')
+    E = np.asarray(T_a, np.float64).reshape(4, 4) @ np.linalg.inv(np.asarray(T_b, np.float64).reshape(4, 4))
+    xi = np.concatenate((rotation_vector(E[:3, :3]), E[:3, 3]))
+    return float(np.sqrt(max(float(xi @ info @ xi), 0.0) / n))

@@ -574,6 +574,62 @@ def validation_counts(label, weights, off, threshold=0.5):
 
 
 # ----------------------------------------------------------------------------
+# geometric fit of registered pairs (csrc/pairscore.hip)
+SCORE_WIDTH = 11   # DGR_SCORE_WIDTH: n, sum d^2, sum q (3), sum q q^T upper triangle (6)
+
+
+def check_score_args(n_rows, bank_off, pair_ids, T, radius):
+    """The host-side arguments of `score_pairs` as the C ABI wants them: (off int64 [nfrag+1], ids int32 [n,2],
+    T float64 [n,16], radius float).  ValueError for offsets that are not [nfrag+1] integers ascending strictly from >= 0
+    to the bank's `n_rows`, a pair list that is empty, not [n,2] integers or names a fragment outside the bank, a T that is
+    not [n,4,4] (or one [4,4] for one pair) or has a non-finite entry in its first three rows, a radius that is not a
+    positive finite number.  Pure host arithmetic: nothing touches the device."""
+    off = np.asarray(bank_off.cpu() if torch.is_tensor(bank_off) else bank_off)
+    if off.ndim != 1 or len(off) < 2 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError('bank_off must be a 1-D integer array [nfrag+1]')
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    if off[0] < 0 or bool((np.diff(off) <= 0).any()) or off[-1] != n_rows:
+        raise ValueError(f'bank_off must ascend strictly (no empty fragment) from >= 0 to the row count {int(n_rows)}')
+    ids = np.asarray(pair_ids.cpu() if torch.is_tensor(pair_ids) else pair_ids)
+    if ids.size == 0:
+        raise ValueError('the pair list is empty')
+    if ids.ndim != 2 or ids.shape[1] != 2 or not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError('pair_ids must be an [n,2] integer array')
+    nfrag = len(off) - 1
+    if bool((ids < 0).any()) or bool((ids >= nfrag).any()):
+        raise ValueError(f'pair id outside [0, {nfrag})')
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    radius, _, _ = check_radius_args(radius, None, np.eye(4), 1)
+    n = len(ids)
+    T = T.detach().cpu().numpy() if torch.is_tensor(T) else np.asarray(T)
+    if T.shape == (4, 4) and n == 1:
+        T = T[None]
+    if T.shape != (n, 4, 4):
+        raise ValueError(f'T must be [{n},4,4], got {T.shape}')
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(n, 16)
+    if not np.isfinite(T[:, :12]).all():
+        raise ValueError('T must be finite (first three rows)')
+    return off, ids, T, radius
+
+
+def score_pairs(bank_xyz, bank_off, pair_ids, T, radius):
+    """Sums of every DIRECTED pair (source fragment, target fragment) of a bank under its pose T[k] (source into the
+    target's frame), over the source rows that have a target row STRICTLY within `radius` (dgr_score_pairs): float64 numpy
+    [n,11] = (n, sum d^2, sum q [3], sum qx qx, qx qy, qx qz, qy qy, qy qz, qz qz) with q the nearest such target row
+    (ties: the smaller row).  bank_xyz [N,3] with fragment f in rows bank_off[f]:bank_off[f+1].
+    `core.pair_score.scores_from_sums` turns the rows into fitness, inlier RMSE and the 6x6 information matrix."""
+    off, ids, T, radius = check_score_args(_rows(bank_xyz, 3, 'bank_xyz'), bank_off, pair_ids, T, radius)
+    lib = _lib.load()
+    xyz = _xyz_dev(bank_xyz)
+    dev = xyz.device
+    out = np.zeros((len(ids), SCORE_WIDTH), np.float64)
+    check(lib.dgr_score_pairs(get_ctx(dev), ptr(xyz), off.ctypes.data_as(_lib.c_i64p), len(off) - 1,
+                              ids.ctypes.data_as(_lib.c_i32p), len(ids), T.ctypes.data_as(_lib.c_f64p), radius,
+                              out.ctypes.data_as(_lib.c_f64p), stream_ptr(dev.index)))
+    return out
+
+
+# ----------------------------------------------------------------------------
 def register_batch(fcgf, inlier, coords0, xyz0, off0, coords1, xyz1, off1, voxel_size,
                    clip_weight_thresh=0.05, inlier_feature_type='coords', max_iter=1000,
                    max_break_count=20, break_threshold_ratio=1e-4, skip_refinement=False,

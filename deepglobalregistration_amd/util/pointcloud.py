@@ -19,3 +19,33 @@ def get_matching_indices(source, target, trans, search_voxel_size, K=None):
     float32 -- what the voxelised clouds of this package are -- with the distances in float64 (csrc/gtmatch.hip)."""
     trans = trans.detach().cpu().numpy() if torch.is_tensor(trans) else np.asarray(trans)
     return ops.radius_pairs(_points(source), _points(target), trans, search_voxel_size, K)
+
+
+def compute_overlap_ratio(pcd0, pcd1, trans, voxel_size, downsample=True):
+    """util/pointcloud.py:72-80: the larger of the two shares of points that have a partner strictly within `voxel_size`
+    -- points of `pcd0` under `trans` against `pcd1`, points of `pcd1` under inv(trans) against `pcd0` -- the quantity
+    behind the `@0.30` 3DMatch pair lists.  `pcd0` / `pcd1`: [N,3] arrays, tensors or objects with `.points`.
+    `downsample=True` voxelises both clouds at `voxel_size` first, as the reference does, but with `ops.voxelize`, which
+    KEEPS THE FIRST POINT of every voxel; Open3D's `voxel_down_sample` AVERAGES the points of a voxel, so the two
+    down-sampled clouds differ by up to a voxel diagonal per point and the ratio is close to, not equal to, the
+    reference's.  `downsample=False` takes the clouds as they are (already voxelised clouds, a bank's fragments).
+    Both directions are one `ops.score_pairs` call on a two-fragment bank."""
+    trans = trans.detach().cpu().numpy() if torch.is_tensor(trans) else np.asarray(trans)
+    if trans.shape != (4, 4):
+        raise ValueError(f'trans must be [4,4], got {trans.shape}')
+    trans = np.array(trans, np.float64)
+    ops.check_radius_args(voxel_size, None, trans, 1)          # fail before anything is moved to the device
+    clouds = []
+    for x in (_points(pcd0), _points(pcd1)):
+        if downsample:
+            x = ops.voxelize(x, voxel_size)[0]
+        elif not torch.is_tensor(x):
+            x = torch.as_tensor(np.asarray(x, np.float32))
+        if x.dim() != 2 or x.shape[1] != 3 or len(x) == 0:
+            raise ValueError(f'expected non-empty [N,3] points, got {tuple(x.shape)}')
+        clouds.append(x.float())
+    clouds[1] = clouds[1].to(clouds[0].device)
+    trans[3] = (0, 0, 0, 1)
+    sums = ops.score_pairs(torch.cat(clouds), [0, len(clouds[0]), len(clouds[0]) + len(clouds[1])], [[0, 1], [1, 0]],
+                           np.stack((trans, np.linalg.inv(trans))), voxel_size)
+    return max(float(sums[0, 0]) / len(clouds[0]), float(sums[1, 0]) / len(clouds[1]))

@@ -375,6 +375,28 @@ int dgr_pairs_isin_batch(dgr_ctx *ctx, const int64_t *pos, const int64_t *pos_of
 int dgr_validation_counts(dgr_ctx *ctx, const uint8_t *label, const float *weights, float threshold,
                           const int64_t *off, int npairs, int64_t *counts_out, dgr_stream stream);
 
+/* Geometric fit of registered pairs of a fragment bank (csrc/pairscore.hip): what the reference's compute_overlap_ratio
+ * (util/pointcloud.py:72-80), Open3D's fitness / inlier_rmse and its GetInformationMatrixFromPointClouds are derived from.
+ * bank_xyz dev f32 [N,3]; bank_off HOST [nfrag + 1], ascending from >= 0 with no empty fragment, as for dgr_register_pairs.
+ * pair_ids HOST [npairs,2]: DIRECTED pairs (source fragment, target fragment); a fragment may occur any number of times on
+ * either side and (i, i) is allowed.  T HOST f64 [npairs,16], row-major 4x4, maps the source into the target's frame (last
+ * row ignored).  For a source row (x, y, z) (f32 widened exactly): p = ((T0 x + T1 y) + T2 z) + T3 per row of T and, for a
+ * target row q, d^2 = (ex^2 + ey^2) + ez^2 with e = p - q, in float64 without fma -- the arithmetic of
+ * dgr_radius_pairs_batch.  The row's PARTNER is the target row minimising (d^2, j) among those with d^2 < radius^2,
+ * STRICTLY: the first entry dgr_radius_pairs_batch(K = 1) lists for the row.  Rows with a non-finite coordinate, on either
+ * side, and source rows whose p is not finite take no part.
+ * sums_out HOST f64 [npairs, DGR_SCORE_WIDTH], over the source rows that have a partner, summed in float64:
+ *   [0] n   [1] sum d^2   [2..4] sum q (x, y, z)   [5..10] sum qx qx, qx qy, qx qz, qy qy, qy qz, qz qz
+ * (a pair without any partner: eleven zeros).  One uniform grid per fragment that occurs as a target, however many pairs it
+ * is the target of; no pair list is written.  Fixed-order reductions, no floating-point atomics: two runs agree bit for
+ * bit, and a pair's eleven values do not depend on the other pairs of the call.  Any npairs >= 1 (launches of 65535 pairs).
+ * DGR_EINVAL before any device work: a NULL argument, npairs < 1, nfrag < 1, radius <= 0 or not finite, a non-finite entry
+ * in the first three rows of a T, offsets that break the bank's rules, a pair id outside [0, nfrag).  Synchronises (twice,
+ * whatever npairs). */
+#define DGR_SCORE_WIDTH 11
+int dgr_score_pairs(dgr_ctx *ctx, const float *bank_xyz, const int64_t *bank_off, int nfrag, const int32_t *pair_ids,
+                    int npairs, const double *T, double radius, double *sums_out, dgr_stream stream);
+
 /* ---- debug entry points (parity tests): the device functions of the registration kernel on their own.
  * ortho2rotation (core/registration.py:16-64) forward for n parameter rows p6 [n,6] -> R9_out [n,9] (row-major 3x3) and,
  * when grad_R9 [n,9] and grad_p6_out [n,6] are given, its backward (what autograd computes for sum(R * grad_R)).
