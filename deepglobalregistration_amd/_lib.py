@@ -35,6 +35,11 @@ class Params(C.Structure):
                 ('ransac_seed', C.c_uint32), ('use_icp', C.c_int)]
 
 
+class PgParams(C.Structure):
+    """dgr_pg_params"""
+    _fields_ = [('mu', C.c_double), ('reference_node', C.c_int), ('max_iter', C.c_int), ('rel_tol', C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/dgr_hip.h
 SIGNATURES = {
     'dgr_last_error': (C.c_char_p, []),
@@ -94,6 +99,8 @@ SIGNATURES = {
     'dgr_pairs_isin_batch': (C.c_int, [vp, vp, c_i64p, vp, c_i64p, C.c_int, c_i64p, vp, vp]),
     'dgr_validation_counts': (C.c_int, [vp, vp, vp, C.c_float, c_i64p, C.c_int, c_i64p, vp]),
     'dgr_score_pairs': (C.c_int, [vp, vp, c_i64p, C.c_int, c_i32p, C.c_int, c_f64p, C.c_double, c_f64p, vp]),
+    'dgr_pose_graph_optimize': (C.c_int, [vp, C.c_int, c_i64p, c_i64p, c_i32p, c_f64p, c_f64p, C.POINTER(C.c_uint8), c_f64p,
+                                          C.POINTER(PgParams), c_f64p, c_f64p, c_f64p, vp]),
     'dgr_debug_ortho2rotation': (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, vp]),
     'dgr_debug_se3_refine_from': (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_double,
                                             c_f64p, c_f64p, vp]),

@@ -404,6 +404,93 @@ class DeepGlobalRegistration:
         out['overlap'] = np.maximum(out['fitness'], out['fitness_reverse'])
         return out
 
+    def optimize_scene(self, bank, pairs, T, scores=None, uncertain=None, radius=None, reference_node=0,
+                       preference_loop_closure=1.0, edge_prune_threshold=0.25, pose_init=None, max_iter=100, rel_tol=1e-13):
+        """One pose per fragment of `bank` in the frame of fragment `reference_node`, from `pairs` ([m,2]: fragment i onto
+        fragment j) and their poses `T` [m,4,4] (what `register_pairs` returned): robust pose-graph optimisation with line
+        processes (`ops.pose_graph_optimize`, csrc/posegraph.hip; `core.pose_graph` states the objective), in the two
+        passes of Open3D's `global_optimization`.
+          * `scores`: what `score_pairs(bank, pairs, T, radius)` returns (computed here when None); its `information` are
+            the edge weights.  Pairs without a correspondence (`n_corr` = 0) are dropped.
+          * `uncertain` [m] bool: the loop closures, subject to a line process; default |i - j| != 1 (consecutive
+            fragments are odometry, as in Open3D's reconstruction pipeline).  All-True is allowed.
+          * mu = preference_loop_closure * radius^2 * mean n_corr (`core.pose_graph.default_mu`); `radius` defaults to
+            2 voxels, the radius `score_pairs` defaults to.
+          * start: the maximum spanning tree by n_corr, certain edges first, unless `pose_init` [n,4,4] is given.
+          * pass 1 over the fragments connected to the reference node; uncertain edges with l < `edge_prune_threshold`
+            are pruned; pass 2 over the kept edges from pass 1's poses (skipped when nothing was pruned: it would repeat
+            pass 1).  Fragments that the kept edges do not connect to the reference node are left out of pass 2 and keep
+            their pass-1 pose (their start when never connected).  A pass takes at most 128 connected fragments.
+        Returns a dict: `poses` [n,4,4] (fragment -> the reference fragment's frame times pose_init[reference_node]),
+        `line_process` [m] (pass 2's, pass 1's for the edges pruned there, NaN for edges that took no part), `kept` [m]
+        bool, `reachable` [n] bool, `objective_initial` / `objective_final` (F* at the start of pass 1 / the end of
+        pass 2), `iterations` and `converged` (both passes), `mu`."""
+        from . import pose_graph as pgm
+        from .fragment_bank import pair_groups
+        bd = torch.device(bank.device)
+        if bd.type != self.device.type or (None not in (bd.index, self.device.index) and bd.index != self.device.index):
+            raise ValueError(f'the bank is on {bank.device}, this object on {self.device}')
+        ids = np.concatenate([g for _, g in pair_groups(bank, pairs, 1)]).astype(np.int64)
+        m, n = len(ids), len(bank)
+        radius = 2 * self.voxel_size if radius is None else radius
+        _, _, T, radius = ops.check_score_args(len(bank.xyz), bank.off, ids, T, radius)
+        T = T.reshape(m, 4, 4).copy()
+        T[:, 3] = (0, 0, 0, 1)
+        if not 0 <= reference_node < n:
+            raise ValueError(f'reference node {reference_node} outside [0, {n})')
+        if not (edge_prune_threshold >= 0 and edge_prune_threshold <= 1):
+            raise ValueError('edge_prune_threshold must lie in [0, 1]')
+        if bool((ids[:, 0] == ids[:, 1]).any()):
+            raise ValueError('a pair joins a fragment to itself')
+        unc = np.abs(ids[:, 0] - ids[:, 1]) != 1 if uncertain is None else np.asarray(uncertain, bool).reshape(-1)
+        if unc.shape != (m,):
+            raise ValueError('one uncertain flag per pair expected')
+        if pose_init is not None:
+            pose_init = np.array(pose_init, np.float64)
+            if pose_init.shape != (n, 4, 4) or not np.isfinite(pose_init).all():
+                raise ValueError(f'pose_init must be [{n},4,4] and finite')
+        if scores is None:
+            scores = self.score_pairs(bank, ids, T, radius)
+        info = np.asarray(scores['information'], np.float64)
+        if info.shape != (m, 6, 6) or not np.isfinite(info).all():
+            raise ValueError(f'scores["information"] must be [{m},6,6] and finite')
+        used = info[:, 3, 3] > 0
+        if not used.any():
+            raise ValueError('no pair has a correspondence')
+        mu = pgm.default_mu(info[used], radius, preference_loop_closure)
+        if pose_init is None:
+            poses, _ = pgm.spanning_tree_poses(n, ids[used], T[used], info[used, 3, 3], reference_node, unc[used])
+        else:
+            poses = pose_init
+        line = np.full(m, np.nan)
+        kept = used.copy()
+        out = {'mu': mu, 'iterations': 0, 'converged': True, 'objective_initial': None, 'objective_final': None}
+        for pass_no in range(2):
+            reach = pgm.reachable_nodes(n, ids, kept, reference_node)
+            sel = kept & reach[ids[:, 0]]           # (an edge has both ends in one component)
+            if not sel.any():
+                break
+            local = np.cumsum(reach) - 1            # node ids of the reachable sub-graph
+            sub = np.nonzero(reach)[0]
+            P, l, stats = ops.pose_graph_optimize([0, len(sub)], [0, int(sel.sum())], local[ids[sel]], T[sel], info[sel],
+                                                  unc[sel], poses[sub], [(mu, int(local[reference_node]), max_iter, rel_tol)],
+                                                  device=self.device)
+            poses = poses.copy()
+            poses[sub] = P
+            line[sel] = l
+            if out['objective_initial'] is None:
+                out['objective_initial'] = float(stats[0, 0])
+            out['objective_final'] = float(stats[0, 1])
+            out['iterations'] += int(stats[0, 2])
+            out['converged'] = out['converged'] and bool(stats[0, 3])
+            if pass_no == 0:                        # prune once, between the passes
+                pruned = sel & unc & (line < edge_prune_threshold)
+                if not pruned.any():
+                    break                           # nothing to drop: pass 2 would repeat pass 1
+                kept = kept & ~pruned
+        out.update(poses=poses, line_process=line, kept=kept, reachable=pgm.reachable_nodes(n, ids, kept, reference_node))
+        return out
+
     # ---- measurement beside the registration path (core/trainer.py:353-489, `_valid_epoch`) ----------------------
     def validate_collated(self, input_dict, matching_radius=None, success_rte_thresh=0.3, success_rre_thresh=15.0, **kw):
         """The validation statistics of the reference's trainer for one collated batch (layout of `register_collated`) that

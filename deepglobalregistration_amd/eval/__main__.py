@@ -1,14 +1,16 @@
 """`python -m deepglobalregistration_amd.eval --threed_match_dir <root> --weights <ckpt>`: the 3DMatch
 trajectory evaluation of scripts/test_3dmatch.py (success = RTE < 0.3 m and RRE < 15 deg by default), or
 `--kitti_dir <root>/dataset --drives 8 9 10` for scripts/test_kitti.py (RTE < 0.6 m, RRE < 5 deg, ground truth
-refined by GPU ICP like the reference's cached poses), on one MI355X.  Needs a real checkpoint and the
+refined by GPU ICP like the reference's cached poses), on one MI355X.  `--batched` registers a scene from features
+computed once per fragment; `--scene` adds the pose-graph optimisation over the scene's scored pairs and writes one
+optimised trajectory per scene.  Needs a real checkpoint and the
 benchmark files; neither is available offline."""
 import argparse
 
 import numpy as np
 import torch
 
-from . import KITTIOdometryPairs, ThreeDMatchTrajectory, evaluate, evaluate_batched, evaluate_kitti
+from . import KITTIOdometryPairs, ThreeDMatchTrajectory, evaluate, evaluate_batched, evaluate_kitti, optimize_scenes
 
 
 def main():
@@ -24,7 +26,11 @@ def main():
     ap.add_argument('--no_icp', action='store_true')
     ap.add_argument('--batched', action='store_true',
                     help='3DMatch: featurise every fragment of a scene once and register its records in fused batches')
-    ap.add_argument('--batch_pairs', type=int, default=6, help='pairs per fused call with --batched')
+    ap.add_argument('--scene', action='store_true',
+                    help='3DMatch: --batched, then robust pose-graph optimisation over each scene\'s scored pairs; writes the '
+                         'optimised trajectory of every scene to --scene_out/<scene>.log')
+    ap.add_argument('--scene_out', default='scene_trajectories')
+    ap.add_argument('--batch_pairs', type=int, default=6, help='pairs per fused call with --batched / --scene')
     ap.add_argument('--out', default='3dmatch-stats_DeepGlobalRegistration.npz')
     args = ap.parse_args()
     from ..core.deep_global_registration import DeepGlobalRegistration
@@ -48,6 +54,12 @@ def main():
     if not args.threed_match_dir:
         ap.error('--threed_match_dir or --kitti_dir is required')
     ds = ThreeDMatchTrajectory(args.threed_match_dir, args.scenes)
+    if args.scene:
+        stats, rows = optimize_scenes(dgr, ds, args.scene_out, args.success_rte_thresh, args.success_rre_thresh,
+                                      batch_pairs=args.batch_pairs)
+        np.savez(args.out, stats=stats, names=['pairwise', 'pose graph'], scenes=ds.scenes,
+                 scene_rows=np.array([r[1:] for r in rows], np.float64))
+        return
     if args.batched:
         stats, scene_means, _ = evaluate_batched(dgr, ds, args.success_rte_thresh, args.success_rre_thresh,
                                                  batch_pairs=args.batch_pairs)

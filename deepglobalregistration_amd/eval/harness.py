@@ -5,7 +5,7 @@ import time
 
 import numpy as np
 
-from .formats import load_cloud, read_trajectory
+from .formats import load_cloud, read_trajectory, write_trajectory
 from .metrics import rte_rre
 
 
@@ -132,3 +132,52 @@ def evaluate_batched(method, dataset, success_rte_thresh=0.3, success_rre_thresh
         if sel.any():
             scene_means[0, sid] = stats[0, sel, :3].mean(0)
     return stats, scene_means, summary
+
+
+def optimize_scenes(method, dataset, out_dir, success_rte_thresh=0.3, success_rre_thresh=15.0, batch_pairs=6, out=print):
+    """The scene mode: per scene, the fragments of its records are featurised once, the records registered
+    (`register_pairs` as in `evaluate_batched`), scored and handed to `method.optimize_scene` -- robust pose-graph
+    optimisation over the scored pairs (csrc/posegraph.hip).  Writes `<out_dir>/<scene>.log`: one record
+    "k k n_fragments" + the 4x4 pose of fragment k in the frame of the scene's first fragment (`write_trajectory`; the
+    trajectory format of the Redwood reconstruction pipeline), for the fragments the kept edges connect to it.
+    Returns (stats [2, pairs, 5], rows): stats[0] judges the pairwise poses as `evaluate_batched` does, stats[1] the
+    poses the optimised trajectory implies for the same records, inv(P_j) P_i (a record with an unreachable fragment
+    counts as a failure); the time column of stats[1] is the optimisation's wall time per record.  rows: per scene
+    (name, fragments, reachable fragments, pairs, kept pairs, objective_initial, objective_final, iterations)."""
+    os.makedirs(out_dir, exist_ok=True)
+    scenes = list(dataset.scenes)
+    stats = np.zeros((2, len(dataset), 5))
+    rows = []
+    k = 0
+    for sid, sname in enumerate(scenes):
+        recs = dataset.records(sname)
+        if not recs:
+            continue
+        t0 = time.time()
+        frags = sorted({f for i, j, _ in recs for f in (i, j)})
+        slot = {f: n for n, f in enumerate(frags)}
+        bank = method.extract_fragments([dataset.fragment(sname, f) for f in frags])
+        pairs = [(slot[i], slot[j]) for i, j, _ in recs]
+        T, _, _ = method.register_pairs(bank, pairs, batch_pairs, safeguard=True, icp=method.use_icp)
+        t1 = time.time()
+        res = method.optimize_scene(bank, pairs, T)
+        t2 = time.time()
+        P, reach = res['poses'], res['reachable']
+        write_trajectory(os.path.join(out_dir, f'{sname}.log'),
+                         [((f, f, len(frags)), P[slot[f]]) for f in frags if reach[slot[f]]])
+        for r, (i, j, pose) in enumerate(recs):
+            T_gt = np.linalg.inv(pose)
+            stats[0, k, :3] = rte_rre(T[r], T_gt, success_rte_thresh, success_rre_thresh)
+            both = reach[slot[i]] and reach[slot[j]]
+            stats[1, k, :3] = rte_rre(np.linalg.inv(P[slot[j]]) @ P[slot[i]] if both else None, T_gt, success_rte_thresh,
+                                      success_rre_thresh)
+            stats[:, k, 3] = ((t1 - t0) / len(recs), (t2 - t1) / len(recs))
+            stats[:, k, 4] = sid
+            k += 1
+        rows.append((sname, len(frags), int(reach.sum()), len(recs), int(res['kept'].sum()), res['objective_initial'],
+                     res['objective_final'], res['iterations']))
+        out(f'{sname}: {len(frags)} fragments ({int(reach.sum())} reachable), {len(recs)} pairs ({int(res["kept"].sum())} kept), '
+            f'F* {res["objective_initial"]:.6g} -> {res["objective_final"]:.6g} in {res["iterations"]} steps')
+    assert k == len(dataset)
+    analyze_stats(stats, np.ones((len(dataset), 1), int), ['pairwise', 'pose graph'], out)
+    return stats, rows

@@ -630,6 +630,109 @@ def score_pairs(bank_xyz, bank_off, pair_ids, T, radius):
 
 
 # ----------------------------------------------------------------------------
+# pose-graph optimisation over scored pairs (csrc/posegraph.hip)
+PG_MAX_NODES = 128   # DGR_PG_MAX_NODES
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def check_pose_graph_args(node_off, edge_off, edge_ids, edge_T, edge_info, edge_uncertain, pose_init, params):
+    """The arguments of `pose_graph_optimize` as the C ABI wants them: (node_off int64 [g+1], edge_off int64 [g+1],
+    ids int32 [E,2], X float64 [E,16], info float64 [E,36], uncertain uint8 [E], poses float64 [N,16], params: one
+    (mu, reference_node, max_iter, rel_tol) tuple per graph).  `params` is one such tuple or dict per graph (`max_iter`
+    and `rel_tol` may be left out: 100, 1e-13).  ValueError for: offsets that are not integers ascending from 0, an empty
+    graph (no nodes or no edges), more than PG_MAX_NODES nodes in a graph, an edge id outside its graph, an edge from a
+    node to itself, a non-finite X, information matrix or initial pose, mu <= 0, a reference node outside the graph, a
+    negative max_iter or rel_tol, arrays whose shapes do not fit.  Pure host arithmetic: nothing touches the device."""
+    offs = []
+    for name, o in (('node_off', node_off), ('edge_off', edge_off)):
+        o = _host(o)
+        if o.ndim != 1 or len(o) < 2 or not np.issubdtype(o.dtype, np.integer):
+            raise ValueError(f'{name} must be a 1-D integer array [ngraphs+1]')
+        o = np.ascontiguousarray(o, dtype=np.int64)
+        if o[0] != 0 or bool((np.diff(o) < 1).any()):
+            raise ValueError(f'{name} must ascend strictly from 0: a graph without nodes or edges is refused')
+        offs.append(o)
+    noff, eoff = offs
+    if len(noff) != len(eoff):
+        raise ValueError('node_off and edge_off must have one entry per graph and one more')
+    ng, N, E = len(noff) - 1, int(noff[-1]), int(eoff[-1])
+    n_of = np.diff(noff)
+    if bool((n_of > PG_MAX_NODES).any()):
+        raise ValueError(f'a graph has {int(n_of.max())} nodes: at most {PG_MAX_NODES} (6 (n - 1) = 762 unknowns and a '
+                         '4.6 MB normal matrix per graph)')
+    ids = _host(edge_ids)
+    if ids.shape != (E, 2) or not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError(f'edge_ids must be an [{E},2] integer array')
+    n_edge = np.repeat(n_of, np.diff(eoff))
+    if bool((ids < 0).any()) or bool((ids >= n_edge[:, None]).any()):
+        raise ValueError('edge id outside its graph')
+    if bool((ids[:, 0] == ids[:, 1]).any()):
+        raise ValueError('an edge joins a node to itself')
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+
+    def mats(a, k, n, name):
+        a = _host(a)
+        if a.shape != (n, k, k):
+            raise ValueError(f'{name} must be [{n},{k},{k}], got {a.shape}')
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(n, k * k)
+        if not np.isfinite(a).all():
+            raise ValueError(f'{name} must be finite')
+        return a
+    X, info, poses = mats(edge_T, 4, E, 'edge_T'), mats(edge_info, 6, E, 'edge_info'), mats(pose_init, 4, N, 'pose_init')
+    unc = _host(edge_uncertain)
+    if unc.shape != (E,):
+        raise ValueError(f'edge_uncertain must be [{E}]')
+    unc = np.ascontiguousarray(unc.astype(bool), dtype=np.uint8)
+    if isinstance(params, dict) or (isinstance(params, tuple) and not isinstance(params[0], (tuple, list, dict))):
+        params = [params]
+    if len(params) != ng:
+        raise ValueError('one parameter record per graph expected')
+    out = []
+    for g, p in enumerate(params):
+        if isinstance(p, dict):
+            p = (p['mu'], p.get('reference_node', 0), p.get('max_iter', 100), p.get('rel_tol', 1e-13))
+        p = tuple(p) + (0, 100, 1e-13)[len(p) - 1:]
+        mu, ref, max_iter, rel_tol = float(p[0]), int(p[1]), int(p[2]), float(p[3])
+        if not (mu > 0 and np.isfinite(mu)):
+            raise ValueError(f'graph {g}: mu must be positive and finite, got {mu!r}')
+        if not 0 <= ref < n_of[g]:
+            raise ValueError(f'graph {g}: reference node {ref} outside [0, {int(n_of[g])})')
+        if not 0 <= max_iter <= 100000:
+            raise ValueError(f'graph {g}: max_iter = {max_iter}')
+        if not (rel_tol >= 0 and np.isfinite(rel_tol)):
+            raise ValueError(f'graph {g}: rel_tol must be >= 0 and finite')
+        out.append((mu, ref, max_iter, rel_tol))
+    return noff, eoff, ids, X, info, unc, poses, out
+
+
+def pose_graph_optimize(node_off, edge_off, edge_ids, edge_T, edge_info, edge_uncertain, pose_init, params, device='cuda'):
+    """Robust pose-graph optimisation with line processes of `ngraphs` independent graphs in one library call
+    (dgr_pose_graph_optimize; one workgroup per graph): graph g owns nodes node_off[g]:node_off[g+1] and edges
+    edge_off[g]:edge_off[g+1]; edge_ids [E,2] = (s, t) LOCAL to the graph, edge_T [E,4,4] the pose of s in t's frame,
+    edge_info [E,6,6], edge_uncertain [E], pose_init [N,4,4], params as for `check_pose_graph_args`.  Host arrays in,
+    host arrays out: (poses [N,4,4], line_process [E], stats [ngraphs,4] = F* initial, F* final, accepted steps,
+    converged).  `core.pose_graph` states the objective; the reference node of every graph keeps its pose bit for bit."""
+    noff, eoff, ids, X, info, unc, poses, prm = check_pose_graph_args(node_off, edge_off, edge_ids, edge_T, edge_info,
+                                                                      edge_uncertain, pose_init, params)
+    lib = _lib.load()
+    dev = torch.device(device)
+    ng = len(noff) - 1
+    cp = (_lib.PgParams * ng)(*[_lib.PgParams(*p) for p in prm])
+    pose_out, line, stats = np.zeros_like(poses), np.zeros(len(ids)), np.zeros((ng, 4))
+    with torch.cuda.device(dev):
+        check(lib.dgr_pose_graph_optimize(get_ctx(dev), ng, noff.ctypes.data_as(_lib.c_i64p), eoff.ctypes.data_as(_lib.c_i64p),
+                                          ids.ctypes.data_as(_lib.c_i32p), X.ctypes.data_as(_lib.c_f64p),
+                                          info.ctypes.data_as(_lib.c_f64p), unc.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          poses.ctypes.data_as(_lib.c_f64p), cp, pose_out.ctypes.data_as(_lib.c_f64p),
+                                          line.ctypes.data_as(_lib.c_f64p), stats.ctypes.data_as(_lib.c_f64p),
+                                          stream_ptr(dev.index)))
+    return pose_out.reshape(-1, 4, 4), line, stats
+
+
+# ----------------------------------------------------------------------------
 def register_batch(fcgf, inlier, coords0, xyz0, off0, coords1, xyz1, off1, voxel_size,
                    clip_weight_thresh=0.05, inlier_feature_type='coords', max_iter=1000,
                    max_break_count=20, break_threshold_ratio=1e-4, skip_refinement=False,

@@ -397,6 +397,42 @@ int dgr_validation_counts(dgr_ctx *ctx, const uint8_t *label, const float *weigh
 int dgr_score_pairs(dgr_ctx *ctx, const float *bank_xyz, const int64_t *bank_off, int nfrag, const int32_t *pair_ids,
                     int npairs, const double *T, double radius, double *sums_out, dgr_stream stream);
 
+/* Robust pose-graph optimisation with line processes over the scored pairs of a scene (csrc/posegraph.hip; Choi, Zhou,
+ * Koltun 2015; the step Open3D's global_optimization runs on .log + .info).  ngraphs independent graphs in one call, one
+ * workgroup each.  ALL pointers are HOST pointers (a graph is a few hundred kilobytes): the library copies in, runs one
+ * persistent kernel and copies out, with one synchronisation at the end.
+ * Graph g has the nodes [node_off[g], node_off[g+1]) and the edges [edge_off[g], edge_off[g+1]) of the arrays (offsets
+ * start at 0).  Edge e: edge_ids[e] = (s, t), node ids LOCAL to its graph; edge_T[e] = X, row-major 4x4, the pose of s in
+ * t's frame (dgr_register_pairs' T of the pair (s, t); taken as rigid, last row ignored); edge_info[e] = Lambda, row-major
+ * 6x6, rotation block first (dgr_score_pairs' sums through the formula at DESIGN.md 4.7); edge_uncertain[e] != 0: a loop
+ * closure subject to a line process.  pose_init [N,16]: row-major 4x4, node -> common frame.
+ *   E = inv(P_t) P_s inv(X),  xi = (rotation vector of E, translation of E),  chi2 = xi^T Lambda xi
+ *   F*(P) = sum_certain chi2 + sum_uncertain mu chi2 / (mu + chi2)
+ * minimised over the poses of every node but reference_node, which keeps its initial value bit for bit, by
+ * Levenberg-Marquardt with the line processes l = (mu / (mu + chi2))^2 frozen inside an outer iteration.  It stops after
+ * max_iter accepted steps, when a step lowers F* by no more than rel_tol F*, when a step's largest entry is below 1e-13,
+ * or when no damping up to 1e8 yields a descent.
+ * pose_out [N,16] (last rows copied from pose_init); line_out [E]: l at the final poses, 1 on certain edges;
+ * stats_out [ngraphs,4] = F* of the initial poses, F* of the final poses, accepted steps, converged (1 / 0).
+ * No floating-point atomics and fixed summation orders: two runs agree bit for bit, and a graph's result does not depend
+ * on the other graphs of the call.
+ * DGR_EINVAL before any device work: a NULL argument, ngraphs < 1, a graph without nodes or edges, more than
+ * DGR_PG_MAX_NODES nodes in a graph (6 (n - 1) = 762 unknowns and a 4.6 MB normal matrix: a factorisation spread over
+ * several workgroups is not implemented), an edge id outside its graph, s == t, a non-finite X (first three rows), Lambda
+ * or initial pose (first three rows), mu <= 0 or not finite, a reference node outside the graph, max_iter < 0, rel_tol < 0
+ * or not finite. */
+#define DGR_PG_MAX_NODES 128
+typedef struct {
+  double mu;            /* > 0: the line-process weight */
+  int reference_node;   /* the gauge: this node keeps its initial pose */
+  int max_iter;         /* accepted steps at most (100 is ample) */
+  double rel_tol;       /* stop when a step lowers F* by no more than rel_tol F* (1e-13) */
+} dgr_pg_params;
+int dgr_pose_graph_optimize(dgr_ctx *ctx, int ngraphs, const int64_t *node_off, const int64_t *edge_off,
+                            const int32_t *edge_ids, const double *edge_T, const double *edge_info,
+                            const uint8_t *edge_uncertain, const double *pose_init, const dgr_pg_params *params,
+                            double *pose_out, double *line_out, double *stats_out, dgr_stream stream);
+
 /* ---- debug entry points (parity tests): the device functions of the registration kernel on their own.
  * ortho2rotation (core/registration.py:16-64) forward for n parameter rows p6 [n,6] -> R9_out [n,9] (row-major 3x3) and,
  * when grad_R9 [n,9] and grad_p6_out [n,6] are given, its backward (what autograd computes for sum(R * grad_R)).
