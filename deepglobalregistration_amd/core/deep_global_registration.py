@@ -491,6 +491,54 @@ class DeepGlobalRegistration:
         out.update(poses=poses, line_process=line, kept=kept, reachable=pgm.reachable_nodes(n, ids, kept, reference_node))
         return out
 
+    def fuse_scene(self, bank, poses, voxel_size=None, fragments=None, min_points=1, clouds=None):
+        """The scene of `bank` under `poses` [n,4,4] (fragment -> common frame: `optimize_scene(...)['poses']`): the points of
+        the selected fragments, each under its pose, averaged per voxel of one lattice with origin 0 (`ops.voxel_mean`,
+        csrc/voxelmean.hip).  `fragments`: a bool mask over the bank or a list of distinct fragment ids, e.g.
+        `res['reachable']` (default: all); `voxel_size` defaults to this object's.  `clouds` (one [N_k,3] float32 / float64
+        array or tensor per fragment of the bank) are fused instead of the bank's voxelised `xyz`: the raw points of the
+        fragments.  Voxels with fewer than `min_points` points are removed.  Returns a dict of device tensors, voxels in the
+        order of their first point: `xyz` float64 [V,3], `count` int32 [V], `first_fragment` int64 [V] (the fragment that
+        voxel's first point belongs to), and `dropped` (int): points that are not finite or leave the int32 lattice.
+        Neither network runs.  The bank's device and the fragment ids are checked as in `score_pairs`."""
+        bd = torch.device(bank.device)
+        if bd.type != self.device.type or (None not in (bd.index, self.device.index) and bd.index != self.device.index):
+            raise ValueError(f'the bank is on {bank.device}, this object on {self.device}')
+        n = len(bank)
+        poses = poses.detach().cpu().numpy() if torch.is_tensor(poses) else np.asarray(poses)
+        if poses.shape != (n, 4, 4):
+            raise ValueError(f'poses must be [{n},4,4], got {poses.shape}')
+        if isinstance(min_points, (bool, np.bool_)) or not isinstance(min_points, (int, np.integer)) or min_points < 1:
+            raise ValueError(f'min_points must be an integer >= 1, got {min_points!r}')
+        voxel_size = self.voxel_size if voxel_size is None else voxel_size
+        if clouds is None:
+            parts, off, rows = None, bank.off, len(bank.xyz)
+        else:
+            if len(clouds) != n:
+                raise ValueError(f'one cloud per fragment of the bank expected: {len(clouds)} for {n}')
+            parts = [c if torch.is_tensor(c) else torch.from_numpy(np.ascontiguousarray(c)) for c in clouds]
+            for k, c in enumerate(parts):
+                if c.dim() != 2 or c.shape[1] != 3 or len(c) == 0 or c.dtype not in (torch.float32, torch.float64):
+                    raise ValueError(f'cloud {k} must be a non-empty float32 / float64 [N,3] array, got {c.dtype} {tuple(c.shape)}')
+            off = np.cumsum([0] + [len(c) for c in parts]).astype(np.int64)
+            rows = int(off[-1])
+        off, ids, _, _, voxel_size, _ = ops.check_voxel_mean_rows(rows, voxel_size, off, np.arange(n) if fragments is None else fragments)
+        T = np.ascontiguousarray(poses[ids], np.float64)
+        if not np.isfinite(T[:, :3]).all():
+            raise ValueError('poses must be finite (first three rows)')
+        if parts is None:
+            xyz = bank.xyz
+        else:   # (one float64 cloud makes the fused array float64: every cloud widens exactly)
+            wide = torch.float64 if any(c.dtype == torch.float64 for c in parts) else torch.float32
+            xyz = torch.cat([c.to(self.device, wide) for c in parts])
+        res = ops.voxel_mean(xyz, voxel_size, off, ids, T)
+        out = {'xyz': res['xyz'], 'count': res['count'], 'dropped': res['dropped'],
+               'first_fragment': torch.bucketize(res['first'], torch.from_numpy(off[1:]).to(res['first'].device), right=True)}
+        if min_points > 1:
+            keep = out['count'] >= int(min_points)
+            out.update({k: out[k][keep] for k in ('xyz', 'count', 'first_fragment')})
+        return out
+
     # ---- measurement beside the registration path (core/trainer.py:353-489, `_valid_epoch`) ----------------------
     def validate_collated(self, input_dict, matching_radius=None, success_rte_thresh=0.3, success_rre_thresh=15.0, **kw):
         """The validation statistics of the reference's trainer for one collated batch (layout of `register_collated`) that

@@ -3,7 +3,7 @@ trajectory evaluation of scripts/test_3dmatch.py (success = RTE < 0.3 m and RRE 
 `--kitti_dir <root>/dataset --drives 8 9 10` for scripts/test_kitti.py (RTE < 0.6 m, RRE < 5 deg, ground truth
 refined by GPU ICP like the reference's cached poses), on one MI355X.  `--batched` registers a scene from features
 computed once per fragment; `--scene` adds the pose-graph optimisation over the scene's scored pairs and writes one
-optimised trajectory per scene.  Needs a real checkpoint and the
+optimised trajectory per scene, and with `--fused_out DIR` the fused cloud of every scene.  Needs a real checkpoint and the
 benchmark files; neither is available offline."""
 import argparse
 
@@ -30,6 +30,10 @@ def main():
                     help='3DMatch: --batched, then robust pose-graph optimisation over each scene\'s scored pairs; writes the '
                          'optimised trajectory of every scene to --scene_out/<scene>.log')
     ap.add_argument('--scene_out', default='scene_trajectories')
+    ap.add_argument('--fused_out', default=None,
+                    help='--scene: also write <DIR>/<scene>.ply, the reachable fragments under their optimised poses averaged '
+                         'per voxel (off by default)')
+    ap.add_argument('--fused_voxel', type=float, default=None, help='voxel size of --fused_out (default: the checkpoint\'s)')
     ap.add_argument('--batch_pairs', type=int, default=6, help='pairs per fused call with --batched / --scene')
     ap.add_argument('--out', default='3dmatch-stats_DeepGlobalRegistration.npz')
     args = ap.parse_args()
@@ -56,7 +60,7 @@ def main():
     ds = ThreeDMatchTrajectory(args.threed_match_dir, args.scenes)
     if args.scene:
         stats, rows = optimize_scenes(dgr, ds, args.scene_out, args.success_rte_thresh, args.success_rre_thresh,
-                                      batch_pairs=args.batch_pairs)
+                                      batch_pairs=args.batch_pairs, fused_dir=args.fused_out, fused_voxel=args.fused_voxel)
         np.savez(args.out, stats=stats, names=['pairwise', 'pose graph'], scenes=ds.scenes,
                  scene_rows=np.array([r[1:] for r in rows], np.float64))
         return

@@ -5,7 +5,7 @@ import time
 
 import numpy as np
 
-from .formats import load_cloud, read_trajectory, write_trajectory
+from .formats import load_cloud, read_trajectory, write_ply, write_trajectory
 from .metrics import rte_rre
 
 
@@ -134,12 +134,15 @@ def evaluate_batched(method, dataset, success_rte_thresh=0.3, success_rre_thresh
     return stats, scene_means, summary
 
 
-def optimize_scenes(method, dataset, out_dir, success_rte_thresh=0.3, success_rre_thresh=15.0, batch_pairs=6, out=print):
+def optimize_scenes(method, dataset, out_dir, success_rte_thresh=0.3, success_rre_thresh=15.0, batch_pairs=6, out=print,
+                    fused_dir=None, fused_voxel=None):
     """The scene mode: per scene, the fragments of its records are featurised once, the records registered
     (`register_pairs` as in `evaluate_batched`), scored and handed to `method.optimize_scene` -- robust pose-graph
     optimisation over the scored pairs (csrc/posegraph.hip).  Writes `<out_dir>/<scene>.log`: one record
     "k k n_fragments" + the 4x4 pose of fragment k in the frame of the scene's first fragment (`write_trajectory`; the
     trajectory format of the Redwood reconstruction pipeline), for the fragments the kept edges connect to it.
+    With `fused_dir`, also `<fused_dir>/<scene>.ply`: the scene itself, the reachable fragments of the bank under their
+    optimised poses averaged per voxel of `fused_voxel` (default: the method's voxel size) by `method.fuse_scene`.
     Returns (stats [2, pairs, 5], rows): stats[0] judges the pairwise poses as `evaluate_batched` does, stats[1] the
     poses the optimised trajectory implies for the same records, inv(P_j) P_i (a record with an unreachable fragment
     counts as a failure); the time column of stats[1] is the optimisation's wall time per record.  rows: per scene
@@ -165,6 +168,10 @@ def optimize_scenes(method, dataset, out_dir, success_rte_thresh=0.3, success_rr
         P, reach = res['poses'], res['reachable']
         write_trajectory(os.path.join(out_dir, f'{sname}.log'),
                          [((f, f, len(frags)), P[slot[f]]) for f in frags if reach[slot[f]]])
+        if fused_dir is not None:
+            os.makedirs(fused_dir, exist_ok=True)
+            fused = method.fuse_scene(bank, P, voxel_size=fused_voxel, fragments=reach)
+            write_ply(os.path.join(fused_dir, f'{sname}.ply'), fused['xyz'].cpu().numpy())
         for r, (i, j, pose) in enumerate(recs):
             T_gt = np.linalg.inv(pose)
             stats[0, k, :3] = rte_rre(T[r], T_gt, success_rte_thresh, success_rre_thresh)

@@ -420,6 +420,12 @@ def _xyz_dev(a, dev=None):
     return t
 
 
+def _xyz_any_dev(a):
+    """[N,3] float32 / float64 points on the current device in their own dtype."""
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t if t.is_cuda else t.to(torch.device('cuda', torch.cuda.current_device()))
+
+
 def icp_point_to_point(source, target, max_correspondence_distance, init=None, max_iter=30,
                        relative_fitness=1e-6, relative_rmse=1e-6):
     """Point-to-point ICP (dgr_icp_point_to_point).  Returns (T [4,4] float64, fitness, inlier_rmse,
@@ -626,6 +632,112 @@ def score_pairs(bank_xyz, bank_off, pair_ids, T, radius):
     check(lib.dgr_score_pairs(get_ctx(dev), ptr(xyz), off.ctypes.data_as(_lib.c_i64p), len(off) - 1,
                               ids.ctypes.data_as(_lib.c_i32p), len(ids), T.ctypes.data_as(_lib.c_f64p), radius,
                               out.ctypes.data_as(_lib.c_f64p), stream_ptr(dev.index)))
+    return out
+
+
+# ----------------------------------------------------------------------------
+# averaging voxel down-sample / scene fusion (csrc/voxelmean.hip)
+VM_FRAC_BITS = 40   # DGR_VM_FRAC_BITS: a voxel's sums count 2^-40 of a voxel
+
+
+def check_voxel_mean_args(xyz, voxel_size, off=None, frag_ids=None, T=None, origin=None):
+    """The host-side arguments of `voxel_mean` as the C ABI wants them: (off int64 [nfrag+1], ids int32 [nsel] or None,
+    T float64 [nsel,16] or None, origin float64 [3], voxel_size float, selected rows).  ValueError for an `xyz` that is not
+    a float32 / float64 [N,3] array or tensor, a voxel size that is not a positive finite number, offsets that are not
+    [nfrag+1] integers ascending strictly from >= 0 to the row count, a fragment list that is empty, not 1-D integers
+    (or a bool mask over the fragments), repeats a fragment or names one outside the bank, a T that is not [nsel,4,4]
+    (or one [4,4] for one fragment) or has a non-finite entry in its first three rows, an origin that is not three finite
+    numbers, 2^31 or more selected rows.  Pure host arithmetic: nothing touches the device."""
+    if not (torch.is_tensor(xyz) or isinstance(xyz, np.ndarray)):
+        raise ValueError('xyz must be a numpy array or a torch tensor')
+    if str(xyz.dtype).replace('torch.', '') not in ('float32', 'float64'):
+        raise ValueError(f'xyz must be float32 or float64, got {xyz.dtype}')
+    return check_voxel_mean_rows(_rows(xyz, 3, 'xyz'), voxel_size, off, frag_ids, T, origin)
+
+
+def check_voxel_mean_rows(n_rows, voxel_size, off=None, frag_ids=None, T=None, origin=None):
+    """`check_voxel_mean_args` behind the check of `xyz` itself, for a point array of `n_rows` rows."""
+    if isinstance(voxel_size, (bool, np.bool_)) or not isinstance(voxel_size, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(voxel_size) or voxel_size <= 0:
+        raise ValueError(f'voxel_size must be a positive finite number, got {voxel_size!r}')
+    if off is None:
+        if n_rows == 0:
+            raise ValueError('empty point cloud')
+        off = np.array([0, n_rows], np.int64)
+    else:
+        off = np.asarray(off.cpu() if torch.is_tensor(off) else off)
+        if off.ndim != 1 or len(off) < 2 or not np.issubdtype(off.dtype, np.integer):
+            raise ValueError('off must be a 1-D integer array [nfrag+1]')
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        if off[0] < 0 or bool((np.diff(off) <= 0).any()) or off[-1] != n_rows:
+            raise ValueError(f'off must ascend strictly (no empty fragment) from >= 0 to the row count {int(n_rows)}')
+    nfrag = len(off) - 1
+    ids = None
+    if frag_ids is not None:
+        ids = np.asarray(frag_ids.cpu() if torch.is_tensor(frag_ids) else frag_ids)
+        if ids.dtype == np.bool_:
+            if ids.shape != (nfrag,):
+                raise ValueError(f'a fragment mask must be [{nfrag}], got {ids.shape}')
+            ids = np.nonzero(ids)[0]
+        if ids.size == 0:
+            raise ValueError('the fragment list is empty')
+        if ids.ndim != 1 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError('frag_ids must be a 1-D integer array or a bool mask over the fragments')
+        if bool((ids < 0).any()) or bool((ids >= nfrag).any()):
+            raise ValueError(f'fragment id outside [0, {nfrag})')
+        if len(np.unique(ids)) != len(ids):
+            raise ValueError('a fragment id is repeated')
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+    nsel = nfrag if ids is None else len(ids)
+    if T is not None:
+        T = T.detach().cpu().numpy() if torch.is_tensor(T) else np.asarray(T)
+        if T.shape == (4, 4) and nsel == 1:
+            T = T[None]
+        if T.shape != (nsel, 4, 4):
+            raise ValueError(f'T must be [{nsel},4,4], got {T.shape}')
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(nsel, 16)
+        if not np.isfinite(T[:, :12]).all():
+            raise ValueError('T must be finite (first three rows)')
+    try:
+        origin = np.zeros(3) if origin is None else np.ascontiguousarray(_host(origin), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('origin must be three finite numbers') from None
+    if origin.shape != (3,) or not np.isfinite(origin).all():
+        raise ValueError('origin must be three finite numbers')
+    rows = int(np.diff(off).sum() if ids is None else (off[ids.astype(np.int64) + 1] - off[ids]).sum())
+    if rows >= 2 ** 31:
+        raise ValueError(f'{rows} selected rows: 2^31 or more')
+    return off, ids, T, origin, float(voxel_size), rows
+
+
+def voxel_mean(xyz, voxel_size, off=None, frag_ids=None, T=None, origin=None, return_sums=False):
+    """Averaging voxel down-sample (dgr_voxel_mean): every occupied voxel of the lattice (`origin`, default 0; `voxel_size`)
+    is replaced by the mean of the points in it.  xyz [N,3] float32 or float64 (quantised in its own dtype widened exactly),
+    fragment f in rows off[f]:off[f+1] (default: one fragment); `frag_ids`: the distinct fragments that take part (ids or a
+    bool mask; default all), T[k] [4,4] the pose of fragment frag_ids[k] into the common frame (default: no transform).
+    Returns a dict of device tensors in ascending order of a voxel's first row of `xyz`: `xyz` float64 [V,3] the means,
+    `coords` int32 [V,3], `count` int32 [V], `first` int64 [V], with `sums` int64 [V,3] when `return_sums` (the fixed-point
+    sums, VM_FRAC_BITS fractional bits: what is bitwise comparable), and `dropped` (int): rows that are not finite or fall
+    outside the int32 lattice.  Integer accumulation: two runs agree bit for bit, whatever the order of the rows."""
+    off, ids, T, origin, voxel_size, rows = check_voxel_mean_args(xyz, voxel_size, off, frag_ids, T, origin)
+    lib = _lib.load()
+    t = _xyz_any_dev(xyz).contiguous()
+    dev = t.device
+    first = torch.empty(rows, dtype=torch.int64, device=dev)
+    coords = torch.empty((rows, 3), dtype=torch.int32, device=dev)
+    count = torch.empty(rows, dtype=torch.int32, device=dev)
+    sums = torch.empty((rows, 3), dtype=torch.int64, device=dev) if return_sums else None
+    mean = torch.empty((rows, 3), dtype=torch.float64, device=dev)
+    n, dropped = C.c_int64(0), C.c_int64(0)
+    check(lib.dgr_voxel_mean(get_ctx(dev), ptr(t), int(t.dtype == torch.float64), off.ctypes.data_as(_lib.c_i64p), len(off) - 1,
+                             None if ids is None else ids.ctypes.data_as(_lib.c_i32p), len(off) - 1 if ids is None else len(ids),
+                             None if T is None else T.ctypes.data_as(_lib.c_f64p), origin.ctypes.data_as(_lib.c_f64p),
+                             voxel_size, ptr(first), ptr(coords), ptr(count), ptr(sums), ptr(mean), C.byref(n),
+                             C.byref(dropped), stream_ptr(dev.index)))
+    V = n.value
+    out = {'xyz': mean[:V], 'coords': coords[:V], 'count': count[:V], 'first': first[:V], 'dropped': int(dropped.value)}
+    if return_sums:
+        out['sums'] = sums[:V]
     return out
 
 

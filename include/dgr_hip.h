@@ -433,6 +433,42 @@ int dgr_pose_graph_optimize(dgr_ctx *ctx, int ngraphs, const int64_t *node_off, 
                             const uint8_t *edge_uncertain, const double *pose_init, const dgr_pg_params *params,
                             double *pose_out, double *line_out, double *stats_out, dgr_stream stream);
 
+/* Averaging voxel down-sample of the selected fragments of a bank, each under its own pose, on ONE lattice
+ * (csrc/voxelmean.hip): every occupied voxel is replaced by the mean of the points that fall into it -- Open3D's
+ * voxel_down_sample, the step in front of the reference's compute_overlap_ratio (util/pointcloud.py:72-80), when one cloud
+ * is given without a pose; the fused scene when all fragments of a scene are given under their optimised poses
+ * (dgr_pose_graph_optimize's pose_out).  Open3D is absent here: the arithmetic below is this library's definition.
+ * xyz dev [N,3], f32 or f64 (is_f64), widened exactly to float64.  off HOST [nfrag + 1], ascending strictly from >= 0 (no
+ * empty fragment), as for dgr_score_pairs: fragment f is rows off[f] .. off[f+1].  frag_ids HOST [nsel]: the DISTINCT
+ * fragments that take part; NULL = all fragments in order (nsel must then be nfrag).  T HOST f64 [nsel,16], row-major 4x4,
+ * T[k] maps fragment frag_ids[k] into the common frame (last row ignored); NULL = no transform.  origin HOST f64 [3].
+ *   transform     for a row (x, y, z): p_r = ((T[r,0] x + T[r,1] y) + T[r,2] z) + T[r,3], r = 0..2, in float64 without fma
+ *                 (the arithmetic of dgr_score_pairs); without T, p is the widened row itself
+ *   quantisation  per axis u = (p - origin) / voxel_size (a correctly rounded float64 division) and c = floor(u): a point
+ *                 exactly on a voxel face belongs to the voxel above it, negative coordinates use floor, not truncation.
+ *                 A row takes part iff all three u are finite and -2^31 <= u < 2^31; the other rows are DROPPED and counted
+ *   accumulation  per row and axis k = floor((u - c) 2^DGR_VM_FRAC_BITS), an integer in [0, 2^40]: u - c is exact except
+ *                 for a negative u so small that it rounds to 1 (k = 2^40, the voxel's upper face), the scaling and the
+ *                 floor are exact.  Per voxel: n = its rows, S[3] = the int64 sums of k.  Integer sums do not depend on
+ *                 the order of the additions: two runs agree bit for bit, and a permutation of the rows permutes nothing
+ *                 but `first`.  2^23 rows per voxel cannot overflow (short of 2^23 rows at k = 2^40).  The quantum is
+ *                 2^-40 of a voxel (4.5e-14 m at 5 cm), far below the f32 inputs
+ *   mean          origin + (c + (double)S / ((double)n 2^40)) voxel_size, in this order, without fma
+ *   order         voxels in ascending order of their FIRST row, a row's number being its row in xyz (so the order of
+ *                 frag_ids does not matter): the order dgr_voxelize gives `sel`
+ * Outputs, all dev with capacity = the number of selected rows: first_out i64 [V] the first row of every voxel,
+ * coords_out i32 [V,3] = c, count_out i32 [V] = n, fsum_out i64 [V,3] = S (NULL: not returned), mean_out f64 [V,3].
+ * *n_out = V and *dropped_out HOST int64: writing them synchronises.  Integer atomics only, no floating-point atomics.
+ * DGR_EINVAL before any device work: a NULL argument (frag_ids, T and fsum_out may be NULL), nfrag < 1, nsel < 1 (or, without
+ * frag_ids, nsel != nfrag), offsets that break the bank's rules, a fragment id outside [0, nfrag) or repeated, a non-finite
+ * entry in the first three rows of a T, a non-finite origin, a voxel_size that is not positive and finite, 2^31 or more
+ * selected rows. */
+#define DGR_VM_FRAC_BITS 40
+int dgr_voxel_mean(dgr_ctx *ctx, const void *xyz, int is_f64, const int64_t *off, int nfrag, const int32_t *frag_ids,
+                   int nsel, const double *T, const double *origin, double voxel_size, int64_t *first_out,
+                   int32_t *coords_out, int32_t *count_out, int64_t *fsum_out, double *mean_out, int64_t *n_out,
+                   int64_t *dropped_out, dgr_stream stream);
+
 /* ---- debug entry points (parity tests): the device functions of the registration kernel on their own.
  * ortho2rotation (core/registration.py:16-64) forward for n parameter rows p6 [n,6] -> R9_out [n,9] (row-major 3x3) and,
  * when grad_R9 [n,9] and grad_p6_out [n,6] are given, its backward (what autograd computes for sum(R * grad_R)).
