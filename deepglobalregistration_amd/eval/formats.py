@@ -124,3 +124,123 @@ def load_cloud(filename):
     if ext in ('.txt', '.xyz'):
         return np.loadtxt(filename)[:, :3]
     raise ValueError(f'unrecognised point-cloud file type: {filename}')
+
+
+# ---- PNG (grayscale depth images) -----------------------------------------------------------------------
+_PNG_MAGIC = b'\x89PNG\r\n\x1a\n'
+
+
+def _png_chunk(tag, data):
+    import zlib
+    return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
+
+
+def write_png_gray16(filename, image, filter_type=0):
+    """A [H,W] uint16 image as a 16-bit grayscale PNG (the 3DMatch depth format; stdlib zlib only).  Every scanline is
+    written with `filter_type` (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth); readers must accept all five."""
+    import zlib
+    img = np.asarray(image)
+    if img.ndim != 2 or img.dtype != np.uint16:
+        raise ValueError(f'expected a [H,W] uint16 image, got {img.dtype} {img.shape}')
+    if filter_type not in (0, 1, 2, 3, 4):
+        raise ValueError(f'PNG filter type {filter_type}')
+    h, w = img.shape
+    raw = img.astype('>u2').view(np.uint8).reshape(h, w * 2).astype(np.int32)
+    bpp = 2
+    left = np.zeros_like(raw)
+    left[:, bpp:] = raw[:, :-bpp]
+    up = np.zeros_like(raw)
+    up[1:] = raw[:-1]
+    upleft = np.zeros_like(raw)
+    upleft[1:, bpp:] = raw[:-1, :-bpp]
+    if filter_type == 0:
+        pred = 0
+    elif filter_type == 1:
+        pred = left
+    elif filter_type == 2:
+        pred = up
+    elif filter_type == 3:
+        pred = (left + up) // 2
+    else:
+        p = left + up - upleft
+        pa, pb, pc = np.abs(p - left), np.abs(p - up), np.abs(p - upleft)
+        pred = np.where((pa <= pb) & (pa <= pc), left, np.where(pb <= pc, up, upleft))
+    rows = np.empty((h, 1 + w * 2), np.uint8)
+    rows[:, 0] = filter_type
+    rows[:, 1:] = ((raw - pred) & 0xff).astype(np.uint8)
+    with open(filename, 'wb') as f:
+        f.write(_PNG_MAGIC)
+        f.write(_png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 16, 0, 0, 0, 0)))
+        f.write(_png_chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)))
+        f.write(_png_chunk(b'IEND', b''))
+
+
+def read_png_gray(filename):
+    """A non-interlaced grayscale PNG of 8 or 16 bits as [H,W] uint8 / uint16 (what `o3d.io.read_image` gives for a
+    depth file), all five scanline filters.  Other colour types, bit depths and interlacing raise ValueError."""
+    import zlib
+    with open(filename, 'rb') as f:
+        data = f.read()
+    if data[:8] != _PNG_MAGIC:
+        raise ValueError(f'{filename}: not a PNG file')
+    pos, idat, hdr = 8, [], None
+    while pos + 8 <= len(data):
+        n, tag = struct.unpack('>I4s', data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if len(body) != n:
+            raise ValueError(f'{filename}: truncated PNG chunk')
+        if tag == b'IHDR':
+            hdr = struct.unpack('>IIBBBBB', body)
+        elif tag == b'IDAT':
+            idat.append(body)
+        elif tag == b'IEND':
+            break
+        pos += 12 + n
+    if hdr is None:
+        raise ValueError(f'{filename}: PNG without IHDR')
+    w, h, depth, colour, comp, filt, interlace = hdr
+    if colour != 0 or depth not in (8, 16) or interlace != 0 or comp != 0 or filt != 0:
+        raise ValueError(f'{filename}: only non-interlaced 8/16-bit grayscale PNG is supported '
+                         f'(colour type {colour}, bit depth {depth}, interlace {interlace})')
+    bpp = depth // 8
+    stride = w * bpp
+    raw = np.frombuffer(zlib.decompress(b''.join(idat)), np.uint8)
+    if raw.size != h * (stride + 1):
+        raise ValueError(f'{filename}: PNG image data has {raw.size} bytes, expected {h * (stride + 1)}')
+    raw = raw.reshape(h, stride + 1)
+    out = np.zeros((h, stride), np.uint8)
+    prev = np.zeros(stride, np.int32)
+    for y in range(h):
+        ft = int(raw[y, 0])
+        line = raw[y, 1:].astype(np.int32)
+        if ft == 0:
+            cur = line
+        elif ft == 2:
+            cur = (line + prev) & 0xff
+        elif ft == 1:       # Sub: a running sum per byte lane
+            cur = line.copy()
+            for b in range(bpp):
+                cur[b::bpp] = np.cumsum(line[b::bpp]) & 0xff
+        elif ft in (3, 4):  # Average / Paeth depend on the reconstructed left neighbour: sequential
+            cur = np.zeros(stride, np.int32)
+            ln, pv = line.tolist(), prev.tolist()
+            c = [0] * stride
+            for i in range(stride):
+                a = c[i - bpp] if i >= bpp else 0
+                b_ = pv[i]
+                if ft == 3:
+                    pr = (a + b_) >> 1
+                else:
+                    cc = pv[i - bpp] if i >= bpp else 0
+                    p = a + b_ - cc
+                    pa, pb, pc = abs(p - a), abs(p - b_), abs(p - cc)
+                    pr = a if (pa <= pb and pa <= pc) else (b_ if pb <= pc else cc)
+                c[i] = (ln[i] + pr) & 0xff
+            cur = np.array(c, np.int32)
+        else:
+            raise ValueError(f'{filename}: PNG filter type {ft}')
+        out[y] = cur.astype(np.uint8)
+        prev = cur
+    if depth == 8:
+        return out
+    return out.view('>u2').astype(np.uint16).reshape(h, w)

@@ -742,6 +742,131 @@ def voxel_mean(xyz, voxel_size, off=None, frag_ids=None, T=None, origin=None, re
 
 
 # ----------------------------------------------------------------------------
+# TSDF fusion of depth frames into a fragment (csrc/tsdf.hip)
+TSDF_BLOCK_LIMIT = 2 ** 26   # DGR_TSDF_BLOCK_LIMIT
+TSDF_FIRST_POINTS, TSDF_FIRST_BLOCKS = 1 << 20, 1 << 10   # tsdf_fragment's first output arrays; it asks again when they are small
+
+
+def check_tsdf_args(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1000.0, depth_trunc=4.5, block=16, stride=4,
+                    min_weight=1):
+    """The host-side arguments of `tsdf_fragment` as the C ABI wants them: (intrinsic float64 [4], pose float64 [F,16],
+    extrinsic float64 [F,16] = inv(pose), (F, H, W)).  ValueError for a `depth` that is not a uint16 [F,H,W] array or tensor
+    with F, H, W >= 1, intrinsics that are not four finite numbers with fx, fy > 0, poses that are not [F,4,4] (or one
+    [4,4] for one frame), not finite or singular, a `block` other than 8 or 16, a voxel length, depth scale or depth
+    truncation that is not a positive finite number, an `sdf_trunc` outside (0, voxel_length * block], `stride` < 1,
+    `min_weight` < 1, 2^28 or more strided pixels.  Pure host arithmetic: nothing touches the device."""
+    if not (torch.is_tensor(depth) or isinstance(depth, np.ndarray)):
+        raise ValueError('depth must be a numpy array or a torch tensor')
+    if str(depth.dtype).replace('torch.', '') != 'uint16':
+        raise ValueError(f'depth must be uint16, got {depth.dtype}')
+    if depth.ndim != 3 or min(depth.shape) < 1:
+        raise ValueError(f'depth must be [F,H,W] with F, H, W >= 1, got {tuple(depth.shape)}')
+    F, H, W = (int(v) for v in depth.shape)
+
+    def number(v, name):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(v) or v <= 0:
+            raise ValueError(f'{name} must be a positive finite number, got {v!r}')
+        return float(v)
+
+    def integer(v, name, ok, what):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not ok(v):
+            raise ValueError(f'{name} must be {what}, got {v!r}')
+        return int(v)
+    voxel_length = number(voxel_length, 'voxel_length')
+    sdf_trunc = number(sdf_trunc, 'sdf_trunc')
+    depth_scale = number(depth_scale, 'depth_scale')
+    depth_trunc = number(depth_trunc, 'depth_trunc')
+    block = integer(block, 'block', lambda v: v in (8, 16), '8 or 16')
+    stride = integer(stride, 'stride', lambda v: v >= 1, 'an integer >= 1')
+    min_weight = integer(min_weight, 'min_weight', lambda v: 1 <= v < 2 ** 31, 'an integer >= 1')
+    if sdf_trunc > voxel_length * block:
+        raise ValueError(f'sdf_trunc {sdf_trunc} exceeds a block ({voxel_length} x {block}): a pixel would touch more than '
+                         f'two blocks per axis')
+    try:
+        intrinsic = np.ascontiguousarray(_host(intrinsic), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('intrinsic must be four finite numbers (fx, fy, cx, cy)') from None
+    if intrinsic.shape != (4,) or not np.isfinite(intrinsic).all():
+        raise ValueError('intrinsic must be four finite numbers (fx, fy, cx, cy)')
+    if intrinsic[0] <= 0 or intrinsic[1] <= 0:
+        raise ValueError('fx and fy must be positive')
+    pose = _host(pose)
+    if pose.shape == (4, 4) and F == 1:
+        pose = pose[None]
+    if pose.shape != (F, 4, 4) or pose.dtype.kind not in 'fiu':
+        raise ValueError(f'pose must be [{F},4,4], got {pose.shape}')
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    if not np.isfinite(pose).all():
+        raise ValueError('pose must be finite')
+    try:
+        extrinsic = np.ascontiguousarray(np.linalg.inv(pose))
+    except np.linalg.LinAlgError:
+        raise ValueError('a pose is singular') from None
+    if not np.isfinite(extrinsic).all():
+        raise ValueError('a pose is singular')
+    if F * (-(-H // stride)) * (-(-W // stride)) >= 2 ** 28:
+        raise ValueError('2^28 or more strided pixels: raise the stride')
+    return intrinsic, pose.reshape(F, 16), extrinsic.reshape(F, 16), (F, H, W)
+
+
+def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1000.0, depth_trunc=4.5, block=16, stride=4,
+                  min_weight=1, return_volume=False, return_stats=False):
+    """TSDF fusion of F depth frames under their camera poses and the surface points of the fused volume
+    (dgr_tsdf_fragment; what the reference's util/integration.py does with Open3D's ScalableTSDFVolume).  depth uint16
+    [F,H,W] (numpy or a device tensor), intrinsic = (fx, fy, cx, cy), pose [F,4,4] float64 camera-to-world as the
+    `.pose.txt` files give it; `extrinsic = inv(pose)` is taken here, on the host.  Blocks of `block`^3 voxels of
+    `voxel_length` are allocated where the pixels on a grid of `stride` see a surface, within `sdf_trunc` of it; every
+    voxel of these blocks is integrated over all frames in order; the points are the zero crossings on the voxels' +x,
+    +y, +z edges whose two ends have at least `min_weight` observations.
+    Returns xyz float64 [P,3] on the device; with `return_volume` a dict with `xyz`, `blocks` int32 [nb,3], `tsdf`
+    float32 [nb, block^3] and `weight` int32 [nb, block^3]; with `return_stats` the dict also has `kept`, the (block,
+    frame) pairs the integration did not cull.  Two calls agree bit for bit."""
+    intrinsic, pose, extrinsic, (F, H, W) = check_tsdf_args(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale,
+                                                            depth_trunc, block, stride, min_weight)
+    lib = _lib.load()
+    if torch.is_tensor(depth):
+        _dev(depth)
+        d = depth.contiguous()
+    else:
+        # torch has no arithmetic on uint16 and older versions no uint16 at all: the bytes travel as int16
+        a = np.ascontiguousarray(depth)
+        d = torch.from_numpy((a if a.flags.writeable else a.copy()).view(np.int16)).cuda()
+    dev = d.device
+    V = block ** 3
+    max_points, max_blocks = TSDF_FIRST_POINTS, TSDF_FIRST_BLOCKS
+    nb, npts, kept = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    while True:
+        xyz = torch.empty((max_points, 3), dtype=torch.float64, device=dev)
+        blocks = tsdf = weight = None
+        if return_volume:
+            blocks = torch.empty((max_blocks, 3), dtype=torch.int32, device=dev)
+            tsdf = torch.empty((max_blocks, V), dtype=torch.float32, device=dev)
+            weight = torch.empty((max_blocks, V), dtype=torch.int32, device=dev)
+        rc = lib.dgr_tsdf_fragment(get_ctx(dev), ptr(d), F, H, W, intrinsic.ctypes.data_as(_lib.c_f64p),
+                                   pose.ctypes.data_as(_lib.c_f64p), extrinsic.ctypes.data_as(_lib.c_f64p),
+                                   float(voxel_length), float(sdf_trunc), float(depth_scale), float(depth_trunc), int(block),
+                                   int(stride), int(min_weight), ptr(xyz), max_points, ptr(blocks), ptr(tsdf), ptr(weight),
+                                   max_blocks if return_volume else 0, C.byref(nb), C.byref(npts),
+                                   C.byref(kept) if return_stats else None, stream_ptr(dev.index))
+        # the one recoverable failure: an output array too small for what the call found -- it says how much it needs
+        if rc == _lib.DGR_ENOMEM and ((return_volume and nb.value > max_blocks) or npts.value > max_points):
+            max_blocks, max_points = max(max_blocks, nb.value), max(max_points, npts.value)
+            continue
+        check(rc)
+        break
+    xyz = xyz[:npts.value]
+    if not (return_volume or return_stats):
+        return xyz
+    out = {'xyz': xyz}
+    if return_volume:
+        out.update(blocks=blocks[:nb.value], tsdf=tsdf[:nb.value], weight=weight[:nb.value])
+    if return_stats:
+        out.update(kept=int(kept.value), n_blocks=int(nb.value))
+    return out
+
+
+# ----------------------------------------------------------------------------
 # pose-graph optimisation over scored pairs (csrc/posegraph.hip)
 PG_MAX_NODES = 128   # DGR_PG_MAX_NODES
 

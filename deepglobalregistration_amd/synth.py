@@ -244,3 +244,74 @@ def gt_correspondences(xyz0, xyz1, T_gt, voxel_size, frac=0.5, seed=0):
     rng = np.random.default_rng(seed)
     take = (d < voxel_size) & (rng.random(len(p)) < frac)
     return np.where(take, j, -1).astype(np.int64)
+
+
+# ----------------------------------------------------------------------------
+# RGB-D sequences (depth only) for the TSDF front end
+# ----------------------------------------------------------------------------
+def synth_rgbd(seed, n_frames, width, height, focal, sweep_deg=40.0, radius=0.5, cam_height=0.3):
+    """A depth sequence of `_indoor_scene`'s recipe (a 4 x 3.5 x 2.6 m room with six cuboids on its floor), ray-cast
+    analytically (ray against axis-aligned box) with its own random stream.  The world origin is the room's CENTRE, so
+    block and voxel coordinates take both signs.  The camera (x right, y down, z forward) moves on an arc of `radius`
+    around the vertical axis at `cam_height` above the centre -- above every cuboid, so it is never inside one --
+    turning through `sweep_deg` while it looks outwards and slightly down.  Returns (depth uint16 [F,H,W] in
+    millimetres, z-depth as a depth camera reports it; (fx, fy, cx, cy); poses float64 [F,4,4] camera-to-world;
+    boxes = [(lo, hi), ...] with the room first).  Deterministic in `seed`; noise-free, so that the boxes are the
+    ground truth of what is fused from it."""
+    rng = np.random.default_rng(seed)
+    room = np.array([4.0, 3.5, 2.6])
+    boxes = [(-room / 2, room / 2)]
+    for _ in range(6):
+        size = rng.uniform(0.3, 1.2, size=3)
+        xy = rng.uniform([0.2, 0.2], room[:2] - size[:2] - 0.2)
+        lo = np.array([xy[0], xy[1], 0.0]) - room / 2
+        boxes.append((lo, lo + size))
+    start = rng.uniform(0, 2 * np.pi)
+    fx = fy = float(focal)
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    xn = (np.arange(width) - cx) / fx
+    yn = (np.arange(height) - cy) / fy
+    dirs_c = np.stack(np.broadcast_arrays(xn[None, :], yn[:, None], 1.0), -1).reshape(-1, 3)   # z-component 1: t IS depth
+    depth = np.zeros((n_frames, height, width), np.uint16)
+    poses = np.tile(np.eye(4), (n_frames, 1, 1))
+    for f in range(n_frames):
+        th = start + np.deg2rad(sweep_deg) * (f / max(n_frames - 1, 1))
+        o = np.array([radius * np.cos(th), radius * np.sin(th), cam_height])
+        fwd = np.array([np.cos(th + 0.3), np.sin(th + 0.3), -0.35])
+        fwd /= np.linalg.norm(fwd)
+        right = np.cross(fwd, [0.0, 0.0, 1.0])
+        right /= np.linalg.norm(right)
+        down = np.cross(fwd, right)
+        R = np.stack([right, down, fwd], 1)
+        poses[f, :3, :3], poses[f, :3, 3] = R, o
+        d = dirs_c @ R.T
+        t_hit = np.full(len(d), np.inf)
+        for k, (lo, hi) in enumerate(boxes):
+            with np.errstate(divide='ignore', invalid='ignore'):
+                t1 = (lo - o) / d
+                t2 = (hi - o) / d
+            tmin = np.nanmax(np.minimum(t1, t2), axis=1)
+            tmax = np.nanmin(np.maximum(t1, t2), axis=1)
+            if k == 0:      # the camera is inside the room: the ray leaves it at tmax
+                t_hit = np.where(tmax > 0, tmax, t_hit)
+            else:
+                ok = (tmax >= tmin) & (tmin > 0)
+                t_hit = np.where(ok & (tmin < t_hit), tmin, t_hit)
+        mm = np.rint(t_hit * 1000.0)
+        depth[f] = np.where(np.isfinite(mm) & (mm < 65535), mm, 0).astype(np.uint16).reshape(height, width)
+    return depth, (fx, fy, cx, cy), poses, boxes
+
+
+def write_rgbd_sequence(directory, depth, intrinsic, poses):
+    """Writes a sequence in the 3DMatch raw layout the reference's util/integration.py reads: `frame-%06d.depth.png`
+    (16-bit grayscale, millimetres), `frame-%06d.pose.txt` (4x4 camera-to-world) and `intrinsics.txt` (3x3 K) in
+    `directory`.  No colour images: the TSDF front end ignores them.  Returns the number of frames."""
+    import os
+    from .eval.formats import write_png_gray16
+    os.makedirs(directory, exist_ok=True)
+    fx, fy, cx, cy = intrinsic
+    np.savetxt(os.path.join(directory, 'intrinsics.txt'), np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]]), fmt='%.17g')
+    for f in range(len(depth)):
+        write_png_gray16(os.path.join(directory, 'frame-%06d.depth.png' % f), depth[f])
+        np.savetxt(os.path.join(directory, 'frame-%06d.pose.txt' % f), np.asarray(poses[f], np.float64), fmt='%.17g')
+    return len(depth)

@@ -1,0 +1,108 @@
+"""Depth frames -> fragments (util/integration.py of the reference): every `n_frames_per_fragment` frames of a 3DMatch-style
+sequence are fused into one TSDF volume on the GPU (`ops.tsdf_fragment`) and the surface points are written as
+`fragment-N.ply`.  Colour is not integrated, so colour files are neither read nor required; the points are the vertices of
+the mesh the reference writes, without its triangles (the loaders read vertices only).
+
+    python -m deepglobalregistration_amd.util.integration DATASET OUTPUT
+"""
+import argparse
+import os
+
+import numpy as np
+
+from ..eval.formats import read_png_gray, write_ply
+
+
+def read_pose(pose_file):
+    """4x4 camera-to-world matrix of a `.pose.txt` file."""
+    pose = np.loadtxt(pose_file, dtype=np.float64)
+    if pose.shape != (4, 4):
+        raise ValueError(f'{pose_file}: expected a 4x4 matrix, got {pose.shape}')
+    return pose
+
+
+def read_intrinsics(intrinsic_file):
+    """(fx, fy, cx, cy) of a 3x3 camera matrix file."""
+    K = np.loadtxt(intrinsic_file, dtype=np.float64)
+    if K.ndim != 2 or K.shape[0] < 2 or K.shape[1] < 3:
+        raise ValueError(f'{intrinsic_file}: expected a 3x3 camera matrix, got {K.shape}')
+    return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+
+
+def read_depth(depth_file):
+    """uint16 [H,W] raw depth (millimetres in 3DMatch) of a 16-bit grayscale PNG."""
+    img = read_png_gray(depth_file)
+    if img.dtype != np.uint16:
+        raise ValueError(f'{depth_file}: expected a 16-bit depth image')
+    return img
+
+
+def integrate_frames_for_fragment(depth_files, pose_files, seq_path, intrinsic, fragment_id, n_frames_per_fragment,
+                                  voxel_length=0.008, sdf_trunc=0.04, relative_to_first=False, **tsdf_args):
+    """The points (float64 [P,3] device tensor) of fragment `fragment_id`: frames [id n, (id + 1) n) of the sorted file
+    lists, fused by `ops.tsdf_fragment` (further keyword arguments go to it).  `relative_to_first`: the fragment in the
+    frame of its first camera (every pose premultiplied by the inverse of the fragment's first)."""
+    from .. import ops
+    start = fragment_id * n_frames_per_fragment
+    end = min(start + n_frames_per_fragment, len(pose_files))
+    if start >= end:
+        raise ValueError(f'fragment {fragment_id} has no frames')
+    depth = np.stack([read_depth(os.path.join(seq_path, depth_files[i])) for i in range(start, end)])
+    pose = np.stack([read_pose(os.path.join(seq_path, pose_files[i])) for i in range(start, end)])
+    if relative_to_first:
+        pose = np.linalg.inv(pose[0]) @ pose
+    return ops.tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, **tsdf_args)
+
+
+def list_sequence(seq_path):
+    """(intrinsic, depth files, pose files) of a sequence directory, found as the reference finds them: sorted
+    `*.depth.png` and `*.pose.txt`, and `intrinsics.txt` in the directory or `camera-intrinsics.txt` one level up."""
+    files = os.listdir(seq_path)
+    if 'intrinsics.txt' in files:
+        intrinsic = read_intrinsics(os.path.join(seq_path, 'intrinsics.txt'))
+    else:
+        intrinsic = read_intrinsics(os.path.join(seq_path, '..', 'camera-intrinsics.txt'))
+    depth_files = sorted(f for f in files if f.endswith('.depth.png'))
+    pose_files = sorted(f for f in files if f.endswith('.pose.txt'))
+    if not depth_files:
+        raise ValueError(f'{seq_path}: no *.depth.png files')
+    if len(depth_files) != len(pose_files):
+        raise ValueError(f'{seq_path}: {len(depth_files)} depth files but {len(pose_files)} pose files')
+    return intrinsic, depth_files, pose_files
+
+
+def process_seq(seq_path, output_path, n_frames_per_fragment=50, voxel_length=0.008, sdf_trunc=0.04,
+                relative_to_first=False, **tsdf_args):
+    """Writes `fragment-{id}.ply` into `output_path` for every `n_frames_per_fragment` frames of the sequence (the last
+    fragment takes what is left).  Returns the files written."""
+    intrinsic, depth_files, pose_files = list_sequence(seq_path)
+    n_fragments = (len(depth_files) + n_frames_per_fragment - 1) // n_frames_per_fragment
+    os.makedirs(output_path, exist_ok=True)
+    written = []
+    for fragment_id in range(n_fragments):
+        xyz = integrate_frames_for_fragment(depth_files, pose_files, seq_path, intrinsic, fragment_id, n_frames_per_fragment,
+                                            voxel_length, sdf_trunc, relative_to_first, **tsdf_args)
+        name = os.path.join(output_path, 'fragment-{}.ply'.format(fragment_id))
+        write_ply(name, xyz.cpu().numpy())
+        written.append(name)
+    return written
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description='Depth integration for a 3DMatch-style raw dataset')
+    parser.add_argument('dataset', help='path to the scene: directories seq* with depth images and poses')
+    parser.add_argument('output', help='path to the output fragments')
+    parser.add_argument('--frames', type=int, default=50, help='frames per fragment')
+    parser.add_argument('--voxel', type=float, default=0.008)
+    parser.add_argument('--relative-to-first', action='store_true', help="fragments in their first camera's frame")
+    args = parser.parse_args(argv)
+    scene_name = os.path.basename(os.path.normpath(args.dataset))
+    output_scene_path = os.path.join(args.output, scene_name)
+    for seq in sorted(s for s in os.listdir(args.dataset) if s.startswith('seq')):
+        files = process_seq(os.path.join(args.dataset, seq), os.path.join(output_scene_path, seq), args.frames, args.voxel,
+                            relative_to_first=args.relative_to_first)
+        print(f'{seq}: {len(files)} fragments -> {os.path.join(output_scene_path, seq)}')
+
+
+if __name__ == '__main__':
+    main()

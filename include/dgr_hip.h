@@ -469,6 +469,51 @@ int dgr_voxel_mean(dgr_ctx *ctx, const void *xyz, int is_f64, const int64_t *off
                    int32_t *coords_out, int32_t *count_out, int64_t *fsum_out, double *mean_out, int64_t *n_out,
                    int64_t *dropped_out, dgr_stream stream);
 
+/* TSDF fusion of the depth frames of one fragment and the surface points of the fused volume (csrc/tsdf.hip): the step the
+ * reference's util/integration.py takes with Open3D's ScalableTSDFVolume.  Open3D is absent here: the arithmetic below is
+ * this library's own restatement of it, and tests/tsdf_ref.py is the same statement in numpy, compared bit for bit.
+ * depth dev uint16 [F,H,W]; intrinsic HOST f64 [4] = (fx, fy, cx, cy), fx, fy > 0; pose HOST f64 [F,16] row-major 4x4
+ * camera-to-world and extrinsic HOST f64 [F,16] = its inverse, world-to-camera, BOTH supplied by the caller (last rows
+ * ignored): the library never inverts a matrix.  All geometry is float64 without fma, every step one correctly rounded
+ * operation in the order written; a rigid transform M is applied per row as ((M0 x + M1 y) + M2 z) + M3.
+ *   pixel        d = raw / depth_scale; the pixel is valid iff raw > 0 and d <= depth_trunc
+ *   blocks       bl = voxel_length block (block = 8 or 16, sdf_trunc <= bl).  Every frame f and every pixel with v % stride
+ *                == 0 and u % stride == 0 that is valid: pc = (((u - cx) / fx) d, ((v - cy) / fy) d, d), pw = pose_f pc, per
+ *                axis lo = floor((pw - sdf_trunc) / bl), hi = floor((pw + sdf_trunc) / bl); a pixel with a lo < -2^26 or a
+ *                hi >= 2^26 (DGR_TSDF_BLOCK_LIMIT) is skipped like an invalid one.  The pixel touches the 8 corners, bit a of
+ *                the corner number choosing hi over lo on axis a, as candidate (((f Hs + vs) Ws + us) 8 + corner), Hs =
+ *                ceil(H / stride), vs = v / stride.  The block list = the distinct block coordinates in ascending order of
+ *                their first candidate.  No valid pixel: zero blocks, zero points, DGR_OK
+ *   integration  voxel i (global integer index; block b holds i = b block + l per axis) has the centre pw = (i + 0.5)
+ *                voxel_length; tsdf f32 = 0 and weight i32 = 0; the frames are applied in the order 0 .. F-1:
+ *                pc = extrinsic_f pw; skip unless z > 0; uf = ((fx x) / z + cx) + 0.5, vf likewise; skip unless 0 <= uf < W
+ *                and 0 <= vf < H; u = (int)uf, v = (int)vf; skip unless the pixel is valid; m = sqrt((1 + ((u - cx) / fx)^2)
+ *                + ((v - cy) / fy)^2); sdf = (d - z) m; skip unless sdf > -sdf_trunc; val = min(1, sdf / sdf_trunc);
+ *                tsdf = (float)(((double)tsdf weight + val) / (weight + 1)), ONE rounding to f32; weight += 1
+ *   points       blocks in list order, voxels by l = (lz block + ly) block + lx, axes a = 0, 1, 2: (f0, w0) the voxel's,
+ *                (f1, w1) its neighbour's at +1 along a (in the neighbouring block where need be; absent if that block is
+ *                not in the list).  A point iff w0, w1 >= min_weight, -0.98f <= f0, f1 < 0.98f and (f0 < 0) != (f1 < 0):
+ *                pw with pw[a] + voxel_length (|f0| / (|f0| + |f1|)) on axis a, |.| taken in float64
+ * Outputs: xyz_out dev f64 [max_points,3] receives the P points.  blocks_out dev i32 [max_blocks,3], tsdf_out dev f32
+ * [max_blocks, block^3], weight_out dev i32 [max_blocks, block^3]: all three or none (NULL); without them the volume lives in
+ * the context's workspace.  *n_blocks_out, *n_points_out HOST: the two values the call synchronises for; *kept_out HOST
+ * (NULL: not counted): the (block, frame) pairs the integration did not cull -- a frame is skipped for a whole block only
+ * when no voxel of the block can pass the tests above, so the cull does not reach the result.
+ * No floating-point atomics: a voxel belongs to one thread and output positions come from scans; two runs agree bit for bit.
+ * DGR_ENOMEM: the workspace cannot be grown, more blocks than max_blocks (reported before the integration) or more points
+ * than max_points (nothing is written to xyz_out) -- *n_blocks_out / *n_points_out then hold what is needed; 2^31 or more
+ * voxel edges.  The library never writes past a capacity.
+ * DGR_EINVAL before any device work: a NULL argument (the three volume outputs and kept_out may be NULL; xyz_out only with
+ * max_points = 0), F, H or W < 1, block not 8 or 16, stride < 1, min_weight < 1, voxel_length, depth_scale or depth_trunc not
+ * positive and finite, sdf_trunc outside (0, bl], non-finite intrinsics, fx or fy <= 0, a non-finite entry in the first
+ * three rows of a pose or an extrinsic, 2^28 or more strided pixels. */
+#define DGR_TSDF_BLOCK_LIMIT 67108864
+int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframes, int height, int width, const double *intrinsic,
+                      const double *pose, const double *extrinsic, double voxel_length, double sdf_trunc,
+                      double depth_scale, double depth_trunc, int block, int stride, int min_weight, double *xyz_out,
+                      int64_t max_points, int32_t *blocks_out, float *tsdf_out, int32_t *weight_out, int64_t max_blocks,
+                      int64_t *n_blocks_out, int64_t *n_points_out, int64_t *kept_out, dgr_stream stream);
+
 /* ---- debug entry points (parity tests): the device functions of the registration kernel on their own.
  * ortho2rotation (core/registration.py:16-64) forward for n parameter rows p6 [n,6] -> R9_out [n,9] (row-major 3x3) and,
  * when grad_R9 [n,9] and grad_p6_out [n,6] are given, its backward (what autograd computes for sum(R * grad_R)).
