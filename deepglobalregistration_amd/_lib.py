@@ -59,6 +59,7 @@ SIGNATURES = {
     'dgr_net_sharers': (C.c_int, [vp]),
     'dgr_resunet_forward': (C.c_int, [vp, vp, vp, vp, C.c_int64, vp, vp]),
     'dgr_net_get_intermediate': (C.c_int, [vp, vp, C.c_char_p, vp, C.c_int64, c_i64p, c_i64p]),
+    'dgr_net_get_tensor': (C.c_int, [vp, vp, C.c_char_p, C.c_int, vp, C.c_int64, c_i64p, c_i64p]),
     'dgr_net_layer_stats': (C.c_int, [vp, vp, C.c_int, c_i64p]),
     'dgr_net_num_layers': (C.c_int, [vp]),
     'dgr_net_rerun_layer': (C.c_int, [vp, vp, C.c_int, C.c_int, c_f32p, c_f32p]),

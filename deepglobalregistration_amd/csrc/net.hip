@@ -70,6 +70,17 @@ struct DgrTensorRef {
   const int32_t *canon = nullptr;   // rows of a coarse 6-D map: library numbering -> first-occurrence numbering
 };
 
+// One named tensor of the last forward in every representation it has (dgr_net_get_tensor): null = not written
+struct DgrTensorRec {
+  const float *f32 = nullptr;            // signed f32 rows (row stride ld)
+  int ld = 0, cols = 0;
+  const uint32_t *amax = nullptr;        // 3-D net: per row the bits of its largest |x| after the pending ReLU
+  const unsigned char *planes = nullptr; // 6-D net: split rows, 4 * cols bytes per row ...
+  const float *scale = nullptr;          // ... and their per-row scale
+  const unsigned char *dsplit = nullptr; // 3-D net: dense split rows, 4 * cols bytes per row
+  const int32_t *n_dev = nullptr, *canon = nullptr;
+};
+
 // The immutable half of a net: the folded, re-tiled weights in HBM.  Shared (reference-counted) by every dgr_net made
 // from it with dgr_net_share -- one context per HIP stream, ONE weight set per device.
 struct DgrWeights {
@@ -101,6 +112,7 @@ struct dgr_net {
   std::shared_ptr<DgrWeights> W;
   LayerRun runs[23];
   std::map<std::string, DgrTensorRef> inter;
+  std::map<std::string, DgrTensorRec> tensors;
   uint64_t run_generation = 0;   // arena generation `runs` / `inter` point into
 };
 
@@ -832,6 +844,27 @@ int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, 
   I["s4_tr"] = {cat4, 256, 128, ms.cm[2].n_dev, ms.cm[2].canon};
   I["s2_tr"] = {cat2, 128, 64, ms.cm[1].n_dev, ms.cm[1].canon};
   I["s1_tr"] = {cat1, 96, 64, ms.cm[0].n_dev};
+  // every named tensor, in the representations this forward really wrote (dgr_net_get_tensor)
+  // (the same names every forward: the entries are overwritten in place)
+  auto reg =[&](const char *name, const Tensor &t, int cols, int lvl) {
+    DgrTensorRec r;
+    r.f32 = (t.split_only || t.dsplit_only) ? nullptr : t.ptr;
+    r.ld = t.ld; r.cols = cols;
+    r.amax = t.amax;
+    r.planes = t.split.planes; r.scale = t.split.scale;
+    r.dsplit = t.dsplit;
+    r.n_dev = ms.cm[lvl].n_dev; r.canon = ms.cm[lvl].canon;
+    net->tensors[name] = r;
+  };
+  reg("T1", T1, 32, 0); reg("Y1", Y1, 32, 0); reg("S1", S1, 32, 0);
+  reg("T2", T2, 64, 1); reg("Y2", Y2, 64, 1); reg("S2", S2, 64, 1);
+  reg("T4", T4, 128, 2); reg("Y4", Y4, 128, 2); reg("S4", S4, 128, 2);
+  reg("T8", T8, 256, 3); reg("Y8", Y8, 256, 3); reg("S8", S8, 256, 3);
+  reg("U4", U4, 128, 2); reg("V4", V4, 128, 2); reg("S4T", S4T, 128, 2); reg("CAT4", CAT4, 256, 2);
+  reg("U2", U2, 64, 1); reg("V2", V2, 64, 1); reg("S2T", S2T, 64, 1); reg("CAT2", CAT2, 128, 1);
+  reg("U1", U1, 64, 0); reg("V1", V1, 64, 0); reg("S1T", S1T, 64, 0); reg("CAT1", CAT1, 96, 0);
+  reg("H", H, 64, 0);
+  reg("OUT", Tensor{out, net->cout, 0}, net->cout, 0);
 
   return DGR_OK;
 }
@@ -1009,6 +1042,48 @@ extern "C" int dgr_net_get_intermediate(dgr_ctx *ctx, dgr_net *net, const char *
         memcpy(host_out + (size_t)canon[p] * t.cols, tmp.data() + (size_t)p * t.cols, (size_t)t.cols * sizeof(float));
     }
     for (int64_t i = 0; i < (int64_t)n * t.cols; ++i) host_out[i] = host_out[i] > 0.f ? host_out[i] : 0.f;
+  }
+  return DGR_OK;
+}
+
+extern "C" int dgr_net_get_tensor(dgr_ctx *ctx, dgr_net *net, const char *name, int repr, void *host_out,
+                                  int64_t capacity_bytes, int64_t *rows, int64_t *row_bytes) {
+  DGR_REQUIRE(ctx && net && name && rows && row_bytes, "NULL argument");
+  auto it = net->tensors.find(name);
+  DGR_REQUIRE(it != net->tensors.end() && it->second.n_dev, "no tensor named '%s' (run a forward first)", name);
+  DGR_REQUIRE(net->run_generation == ctx->arena.generation,
+              "the activations of the last forward are gone: a later call on this context reused its workspace");
+  const DgrTensorRec &t = it->second;
+  const void *src = nullptr;
+  size_t rb = 0, ld = 0;   // bytes per row: returned / in memory
+  const char *what = "";
+  switch (repr) {
+    case DGR_TENSOR_F32: src = t.f32; rb = (size_t)t.cols * 4; ld = (size_t)t.ld * 4; what = "f32 rows"; break;
+    case DGR_TENSOR_AMAX: src = t.amax; rb = ld = 4; what = "row maxima"; break;
+    case DGR_TENSOR_SPLIT_PLANES: src = t.planes; rb = ld = (size_t)t.cols * 4; what = "split rows"; break;
+    case DGR_TENSOR_SPLIT_SCALE: src = t.scale; rb = ld = 4; what = "split-row scales"; break;
+    case DGR_TENSOR_DENSE_SPLIT: src = t.dsplit; rb = ld = (size_t)t.cols * 4; what = "dense split rows"; break;
+    default: DGR_REQUIRE(false, "dgr_net_get_tensor: unknown representation %d", repr);
+  }
+  DGR_REQUIRE(src != nullptr, "the last forward did not write tensor '%s' as %s", name, what);
+  int32_t n = 0;
+  DGR_HIP_CHECK(hipDeviceSynchronize());
+  DGR_HIP_CHECK(hipMemcpy(&n, t.n_dev, sizeof(int32_t), hipMemcpyDeviceToHost));
+  *rows = n;
+  *row_bytes = (int64_t)rb;
+  if (!host_out) return DGR_OK;
+  DGR_REQUIRE(capacity_bytes >= (int64_t)n * (int64_t)rb, "host buffer too small");
+  if (!t.canon) {
+    DGR_HIP_CHECK(hipMemcpy2D(host_out, rb, src, ld, rb, (size_t)n, hipMemcpyDeviceToHost));
+  } else {   // rows back in first-occurrence order (coarse 6-D maps are numbered in bucket order)
+    std::vector<unsigned char> tmp((size_t)n * rb);
+    std::vector<int32_t> canon(n);
+    DGR_HIP_CHECK(hipMemcpy2D(tmp.data(), rb, src, ld, rb, (size_t)n, hipMemcpyDeviceToHost));
+    DGR_HIP_CHECK(hipMemcpy(canon.data(), t.canon, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int32_t p = 0; p < n; ++p) {
+      DGR_REQUIRE(canon[p] >= 0 && canon[p] < n, "dgr_net_get_tensor: row numbering out of range");
+      memcpy(static_cast<unsigned char *>(host_out) + (size_t)canon[p] * rb, tmp.data() + (size_t)p * rb, rb);
+    }
   }
   return DGR_OK;
 }

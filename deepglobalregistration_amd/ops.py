@@ -147,6 +147,23 @@ class NetHandle:
                                            C.byref(rows), C.byref(cols)))
         return buf
 
+    TENSOR_REPRS = {'f32': (0, np.float32), 'amax': (1, np.uint32), 'split_planes': (2, np.uint8),
+                    'split_scale': (3, np.float32), 'dense_split': (4, np.uint8)}
+
+    def tensor(self, name, repr='f32'):
+        """Named tensor `name` of the last forward in representation `repr` (dgr_net_get_tensor; test instrument):
+        'f32' [n, C] signed rows, 'amax' [n] uint32, 'split_planes' [n, 4 C] bytes, 'split_scale' [n], 'dense_split'
+        [n, 4 C] bytes.  Raises if the forward did not write that representation."""
+        lib = _lib.load()
+        code, dtype = self.TENSOR_REPRS[repr]
+        rows, rb = C.c_int64(0), C.c_int64(0)
+        ctx = get_ctx(self.device)
+        check(lib.dgr_net_get_tensor(ctx, self.handle, name.encode(), code, None, 0, C.byref(rows), C.byref(rb)))
+        buf = np.empty((rows.value, rb.value // np.dtype(dtype).itemsize), dtype)
+        check(lib.dgr_net_get_tensor(ctx, self.handle, name.encode(), code, buf.ctypes.data, buf.nbytes,
+                                     C.byref(rows), C.byref(rb)))
+        return buf[:, 0] if repr in ('amax', 'split_scale') else buf
+
     def debug_conv_layer(self, layer, coords, feats, relu=False):
         """Conv layer `layer` (forward order) applied to `feats` [N, Cin] over the 3^D same-stride map of `coords`,
         through the kernels the forward uses for it (dgr_debug_conv_layer; test instrument)."""

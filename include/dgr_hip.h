@@ -138,6 +138,27 @@ int dgr_resunet_forward(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, const
  * to a HOST buffer (post-ReLU values, like the reference's out_s* tensors); rows/cols out. */
 int dgr_net_get_intermediate(dgr_ctx *ctx, dgr_net *net, const char *name, float *host_out,
                              int64_t capacity, int64_t *rows, int64_t *cols);
+/* Test instrument: after a forward, copy one named tensor of it to a HOST buffer in one of the representations the
+ * forward really wrote.  name: "T1" "Y1" "S1" "T2" "Y2" "S2" "T4" "Y4" "S4" "T8" "Y8" "S8" "U4" "V4" "S4T" "U2" "V2"
+ * "S2T" "U1" "V1" "S1T" "H" (the activations in forward order; Y / V: the middle tensor of a residual block), the
+ * concatenation buffers "CAT4" "CAT2" "CAT1" (decoder half first), and "OUT" (the caller's output buffer of that
+ * forward, which must still be allocated).  repr:
+ *   DGR_TENSOR_F32           f32 rows as they lie in memory: signed, the tensor's pending ReLU not applied
+ *   DGR_TENSOR_AMAX          3-D net: per row one uint32, the bits of the row's largest |x| after the pending ReLU
+ *   DGR_TENSOR_SPLIT_PLANES  6-D net: the split rows a wide layer gathers, 4 * channels bytes per row (per 64 channels
+ *                            128 bytes of the f16 piece h, then 128 bytes of the piece m; pending ReLU applied)
+ *   DGR_TENSOR_SPLIT_SCALE   ... and their power-of-two scale, one float per row: x = (h + m) / scale
+ *   DGR_TENSOR_DENSE_SPLIT   3-D net: the dense split rows, 4 * channels raw bytes per row
+ * A representation the forward did not write (e.g. the f32 rows of a block's middle tensor that exists as pieces only)
+ * is an error, never stale memory.  Rows come back in first-occurrence order, like dgr_net_get_intermediate.
+ * rows / row_bytes are always returned; host_out may be NULL to query them.  Synchronises the device. */
+#define DGR_TENSOR_F32 0
+#define DGR_TENSOR_AMAX 1
+#define DGR_TENSOR_SPLIT_PLANES 2
+#define DGR_TENSOR_SPLIT_SCALE 3
+#define DGR_TENSOR_DENSE_SPLIT 4
+int dgr_net_get_tensor(dgr_ctx *ctx, dgr_net *net, const char *name, int repr, void *host_out,
+                       int64_t capacity_bytes, int64_t *rows, int64_t *row_bytes);
 /* per-forward work statistics of the last forward (for the roofline report): for conv layer
  * `layer` (0..22): pairs, non-empty offsets, n_in, n_out, cin, cout.  Synchronises. */
 int dgr_net_layer_stats(dgr_ctx *ctx, dgr_net *net, int layer, int64_t stats[8]);
