@@ -8,114 +8,20 @@
 // distances are ordered by the smaller index here (FLANN leaves them in tree order), which makes the list a function of
 // the input alone.  The transformation and the distances are float64 on the f32 points widened exactly, in a fixed
 // operation order without fma, so that a host restatement (tests, tests/golden/make_golden_gt_match.py) gets the same bits.
-#include "dgr_internal.h"
+#include "pointgrid.h"
 
 #include <cmath>
 #include <cstring>
 
 constexpr int GT_THREADS = 256;
-constexpr int32_t GT_CELL_CAP = 1 << 20;   // grid cells per pair (the cell edge doubles until the grid fits)
-constexpr int GT_MAX_PAIRS = 65535;        // pairs are the y dimension of the launches
+constexpr int GT_MAX_PAIRS = 65535;   // pairs are the y dimension of the launches
 
-// per pair: pose, row ranges and the uniform grid over the pair's finite target points
+// per pair: pose and source rows; the uniform grid over the pair's finite target points is grid number p of the call
 struct GtPair {
   double T[12];                // [R | t] row-major 3x4
-  double gmin[3], cell;
-  int64_t off0, off1;          // first row of the pair in xyz0 / xyz1
-  int64_t cell_base;           // first cell of the pair in the batch's concatenated cell arrays
-  int32_t n0, n1;
-  int32_t gdim[3], ncell;      // ncell = 0: no finite target point
-  uint32_t bmin[3], bmax[3];   // ordered-uint bounding box of the finite target points
+  int64_t off0;                // first row of the pair in xyz0
+  int32_t n0;
 };
-
-__device__ __forceinline__ uint32_t gt_ord_f32(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float gt_unord_f32(uint32_t k) {
-  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
-}
-__device__ __forceinline__ bool gt_finite3(const float *p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
-
-__global__ void __launch_bounds__(GT_THREADS) gt_bbox_kernel(const float *__restrict__ xyz1, GtPair *pairs) {
-  GtPair *P = pairs + blockIdx.y;
-  const int64_t j = (int64_t)blockIdx.x * GT_THREADS + threadIdx.x;
-  if ((int64_t)blockIdx.x * GT_THREADS >= P->n1) return;   // block-uniform
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  if (j < P->n1) {
-    const float *q = xyz1 + (P->off1 + j) * 3;
-    if (gt_finite3(q))
-      for (int d = 0; d < 3; ++d) lo[d] = hi[d] = gt_ord_f32(q[d]);
-  }
-  for (int s = 32; s >= 1; s >>= 1)
-    for (int d = 0; d < 3; ++d) {
-      lo[d] = min(lo[d], (uint32_t)__shfl_xor((int)lo[d], s, 64));
-      hi[d] = max(hi[d], (uint32_t)__shfl_xor((int)hi[d], s, 64));
-    }
-  if ((threadIdx.x & 63) == 0)
-    for (int d = 0; d < 3; ++d) { atomicMin(&P->bmin[d], lo[d]); atomicMax(&P->bmax[d], hi[d]); }
-}
-
-// Uniform grid per pair: cell edge >= radius (doubled until the grid fits GT_CELL_CAP), so that every target point closer
-// than the radius lies in the 27 cells around the query's.  The edge starts a hair ABOVE the radius: a query and a hit
-// are then less than (1 - 1e-7) cells apart along every axis and the rounding of the two cell computations (~1e-10 cells at
-// 2^20 cells per axis) cannot put them two cells apart.  Then the pairs' cell ranges back to back (serial: npairs is small).
-__global__ void gt_layout_kernel(GtPair *pairs, int npairs, double radius, int64_t *total_cells) {
-  for (int p = threadIdx.x; p < npairs; p += blockDim.x) {
-    GtPair *P = pairs + p;
-    P->ncell = 0;
-    P->gdim[0] = P->gdim[1] = P->gdim[2] = 0;
-    P->cell = radius;
-    P->gmin[0] = P->gmin[1] = P->gmin[2] = 0.0;
-    if (P->bmin[0] > P->bmax[0]) continue;   // no finite target point
-    double lo[3], hi[3];
-    for (int d = 0; d < 3; ++d) { lo[d] = (double)gt_unord_f32(P->bmin[d]); hi[d] = (double)gt_unord_f32(P->bmax[d]); }
-    double cell = radius * (1.0 + 1e-7);
-    for (int tries = 0; tries < 2200; ++tries) {   // (2^2200 passes the exponent range: the loop ends by fitting)
-      double total = 1.0;
-      for (int d = 0; d < 3; ++d) total *= floor((hi[d] - lo[d]) / cell) + 1.0;
-      if (total <= (double)GT_CELL_CAP) break;
-      cell *= 2.0;
-    }
-    int64_t total = 1;
-    for (int d = 0; d < 3; ++d) {
-      P->gmin[d] = lo[d];
-      P->gdim[d] = (int32_t)(floor((hi[d] - lo[d]) / cell) + 1.0);
-      total *= P->gdim[d];
-    }
-    P->cell = cell;
-    P->ncell = (int32_t)total;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t base = 0;
-    for (int p = 0; p < npairs; ++p) { pairs[p].cell_base = base; base += pairs[p].ncell; }
-    *total_cells = base;
-  }
-}
-
-__device__ __forceinline__ int gt_cell_of(const GtPair *P, const float *q) {
-  const int cx = (int)floor(((double)q[0] - P->gmin[0]) / P->cell), cy = (int)floor(((double)q[1] - P->gmin[1]) / P->cell),
-            cz = (int)floor(((double)q[2] - P->gmin[2]) / P->cell);
-  return (cz * P->gdim[1] + cy) * P->gdim[0] + cx;
-}
-
-// grid build, pass 1 (FILL = false): points per cell; pass 2: every finite target point into its cell's range as
-// (x, y, z, bits of the pair-local row index).  The order inside a cell is whatever the atomic cursors give: the
-// (d^2, j) rank of the search does not depend on it.
-template <bool FILL>
-__global__ void __launch_bounds__(GT_THREADS)
-    gt_grid_kernel(const float *__restrict__ xyz1, const GtPair *__restrict__ pairs, int32_t *__restrict__ counts,
-                   const int32_t *__restrict__ starts, float4 *__restrict__ sorted) {
-  const GtPair *P = pairs + blockIdx.y;
-  const int64_t j = (int64_t)blockIdx.x * GT_THREADS + threadIdx.x;
-  if (j >= P->n1) return;
-  const float *q = xyz1 + (P->off1 + j) * 3;
-  if (!gt_finite3(q)) return;
-  const int64_t c = P->cell_base + gt_cell_of(P, q);
-  const int32_t k = atomicAdd(&counts[c], 1);
-  if (FILL) sorted[starts[c] + k] = make_float4(q[0], q[1], q[2], __int_as_float((int32_t)j));
-}
 
 // One thread per source row.  FILL = false: the number of hits (capped at K when K > 0).  FILL = true: every hit whose rank
 // by (d^2, j) among the row's hits is below the cap goes to pairs_out[row_off[row] + rank] -- the rank comes from a second
@@ -123,55 +29,29 @@ __global__ void __launch_bounds__(GT_THREADS)
 // candidates of the 27 cells, a few dozen on voxelised clouds.  Neighbouring threads own neighbouring output segments.
 template <bool FILL>
 __global__ void __launch_bounds__(GT_THREADS)
-    gt_radius_kernel(const float *__restrict__ xyz0, const GtPair *__restrict__ pairs, const int32_t *__restrict__ starts,
-                     const float4 *__restrict__ sorted, double r2, int32_t K, int32_t *__restrict__ counts_out,
-                     const int64_t *__restrict__ row_off, longlong2 *__restrict__ pairs_out) {
-#pragma clang fp contract(off)   // the distances are DEFINED without fma (see the head of this file)
+    gt_radius_kernel(const float *__restrict__ xyz0, const GtPair *__restrict__ pairs, const DgrPointGrid *__restrict__ grids,
+                     const int32_t *__restrict__ starts, const float4 *__restrict__ sorted, double r2, int32_t K,
+                     int32_t *__restrict__ counts_out, const int64_t *__restrict__ row_off, longlong2 *__restrict__ pairs_out) {
   const GtPair *P = pairs + blockIdx.y;
+  const DgrPointGrid &G = grids[blockIdx.y];
   const int64_t i = (int64_t)blockIdx.x * GT_THREADS + threadIdx.x;
   if (i >= P->n0) return;
   const int64_t row = P->off0 + i;
-  const float *s = xyz0 + row * 3;
-  const double x = (double)s[0], y = (double)s[1], z = (double)s[2];
-  const double px = ((P->T[0] * x + P->T[1] * y) + P->T[2] * z) + P->T[3];
-  const double py = ((P->T[4] * x + P->T[5] * y) + P->T[6] * z) + P->T[7];
-  const double pz = ((P->T[8] * x + P->T[9] * y) + P->T[10] * z) + P->T[11];
+  double px, py, pz;
+  dgr_pose_apply(P->T, xyz0 + row * 3, &px, &py, &pz);
   int32_t n = 0;
-  if (P->ncell > 0 && isfinite(px) && isfinite(py) && isfinite(pz)) {   // (a non-finite source row transforms to non-finite)
-    // the query's cell, clamped to two cells outside the grid (farther queries cannot have a hit)
-    const int cx = (int)fmin(fmax(floor((px - P->gmin[0]) / P->cell), -2.0), (double)P->gdim[0] + 1.0);
-    const int cy = (int)fmin(fmax(floor((py - P->gmin[1]) / P->cell), -2.0), (double)P->gdim[1] + 1.0);
-    const int cz = (int)fmin(fmax(floor((pz - P->gmin[2]) / P->cell), -2.0), (double)P->gdim[2] + 1.0);
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, P->gdim[0] - 1);   // the cells of a row of the grid are contiguous
-    const int32_t *st = starts + P->cell_base;
+  if (G.ncell > 0 && isfinite(px) && isfinite(py) && isfinite(pz)) {   // (a non-finite source row transforms to non-finite)
     const int64_t out0 = FILL ? row_off[row] : 0;
-    if (x0 <= x1)
-      for (int a = 0; a < 9; ++a) {
-        const int zz = cz + a / 3 - 1, yy = cy + a % 3 - 1;
-        if (zz < 0 || zz >= P->gdim[2] || yy < 0 || yy >= P->gdim[1]) continue;
-        const int rowc = (zz * P->gdim[1] + yy) * P->gdim[0];
-        for (int32_t e = st[rowc + x0]; e < st[rowc + x1 + 1]; ++e) {
-          const float4 q = sorted[e];
-          const double ex = px - (double)q.x, ey = py - (double)q.y, ez = pz - (double)q.z;
-          const double d2 = (ex * ex + ey * ey) + ez * ez;
-          if (!(d2 < r2)) continue;
-          if (!FILL) { ++n; continue; }
-          const int32_t j = __float_as_int(q.w);
-          int32_t rank = 0;
-          for (int b = 0; b < 9; ++b) {
-            const int z2 = cz + b / 3 - 1, y2 = cy + b % 3 - 1;
-            if (z2 < 0 || z2 >= P->gdim[2] || y2 < 0 || y2 >= P->gdim[1]) continue;
-            const int rc2 = (z2 * P->gdim[1] + y2) * P->gdim[0];
-            for (int32_t f = st[rc2 + x0]; f < st[rc2 + x1 + 1]; ++f) {
-              const float4 o = sorted[f];
-              const double fx = px - (double)o.x, fy = py - (double)o.y, fz = pz - (double)o.z;
-              const double o2 = (fx * fx + fy * fy) + fz * fz;
-              rank += (o2 < d2 || (o2 == d2 && __float_as_int(o.w) < j)) ? 1 : 0;   // (o2 <= d2 < r2: a hit itself)
-            }
-          }
-          if (K == 0 || rank < K) pairs_out[out0 + rank] = make_longlong2((long long)i, (long long)j);
-        }
-      }
+    dgr_grid_visit(G, starts, sorted, px, py, pz, [&](const float4 &q, double d2) {
+      if (!(d2 < r2)) return;
+      if (!FILL) { ++n; return; }
+      const int32_t j = __float_as_int(q.w);
+      int32_t rank = 0;
+      dgr_grid_visit(G, starts, sorted, px, py, pz, [&](const float4 &o, double o2) {
+        rank += (o2 < d2 || (o2 == d2 && __float_as_int(o.w) < j)) ? 1 : 0;   // (o2 <= d2 < r2: a hit itself)
+      });
+      if (K == 0 || rank < K) pairs_out[out0 + rank] = make_longlong2((long long)i, (long long)j);
+    });
   }
   if (!FILL) counts_out[row] = (K > 0 && n > K) ? K : n;
 }
@@ -265,64 +145,50 @@ extern "C" int dgr_radius_pairs_batch(dgr_ctx *ctx, const float *xyz0, const int
   DGR_CHECK(ctx->arena.reset());
   DgrArena &A = ctx->arena;
   std::vector<GtPair> host(npairs);
-  int64_t max0 = 0, max1 = 0;
+  std::vector<DgrPointGrid> hgrids(npairs);
+  int64_t max0 = 0;
   for (int p = 0; p < npairs; ++p) {
     GtPair &P = host[p];
     memset(&P, 0, sizeof(P));
     memcpy(P.T, T + (size_t)p * 16, 12 * sizeof(double));
-    P.off0 = off0[p]; P.off1 = off1[p];
-    P.n0 = (int32_t)(off0[p + 1] - off0[p]); P.n1 = (int32_t)(off1[p + 1] - off1[p]);
-    for (int d = 0; d < 3; ++d) { P.bmin[d] = 0xffffffffu; P.bmax[d] = 0u; }
-    max0 = std::max<int64_t>(max0, P.n0); max1 = std::max<int64_t>(max1, P.n1);
+    P.off0 = off0[p];
+    P.n0 = (int32_t)(off0[p + 1] - off0[p]);
+    max0 = std::max<int64_t>(max0, P.n0);
+    memset(&hgrids[p], 0, sizeof(DgrPointGrid));
+    hgrids[p].off = off1[p];
+    hgrids[p].n = (int32_t)(off1[p + 1] - off1[p]);
   }
   GtPair *pairs;
-  int64_t *totals;   // [0] cells of the batch, [1] pairs of the batch
+  int64_t *total_pairs;
   DGR_ALLOC(pairs, A, GtPair, npairs);
-  DGR_ALLOC(totals, A, int64_t, 2);
+  DGR_ALLOC(total_pairs, A, int64_t, 1);
   DGR_HIP_CHECK(hipMemcpyAsync(pairs, host.data(), (size_t)npairs * sizeof(GtPair), hipMemcpyHostToDevice, stream));
-  const dim3 g0((unsigned)dgr_ceil_div(max0, GT_THREADS), npairs), g1((unsigned)dgr_ceil_div(max1, GT_THREADS), npairs);
-  if (max1 > 0) gt_bbox_kernel<<<g1, GT_THREADS, 0, stream>>>(xyz1, pairs);
-  gt_layout_kernel<<<1, GT_THREADS, 0, stream>>>(pairs, npairs, radius, totals);
-  DGR_LAUNCH_CHECK();
-  // the cell count of the batch sizes the grid's arrays (a 3DMatch fragment at 10-cm cells has ~10^5 cells, not the cap)
   unsigned char *pin;
   DGR_CHECK(dgr_ctx_pinned(ctx, 64, &pin));
   volatile int64_t *landed = reinterpret_cast<volatile int64_t *>(pin);
-  DGR_HIP_CHECK(hipMemcpyAsync(pin, totals, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  DGR_CHECK(dgr_ctx_wait(ctx, stream));
-  const int64_t ncell = landed[0];
-  DGR_REQUIRE(ncell >= 0 && ncell < INT32_MAX - 1, "dgr_radius_pairs_batch: %lld grid cells in the batch", (long long)ncell);
-
-  int32_t *cell_count, *cell_start, *cursor;
-  float4 *sorted;
-  DGR_ALLOC(cell_count, A, int32_t, ncell + 1);
-  DGR_ALLOC(cell_start, A, int32_t, ncell + 1);
-  DGR_ALLOC(cursor, A, int32_t, ncell + 1);
-  DGR_ALLOC(sorted, A, float4, n1_all);
-  DGR_HIP_CHECK(hipMemsetAsync(cell_count, 0, (size_t)(ncell + 1) * sizeof(int32_t), stream));
-  DGR_HIP_CHECK(hipMemsetAsync(cursor, 0, (size_t)(ncell + 1) * sizeof(int32_t), stream));
-  if (ncell > 0) gt_grid_kernel<false><<<g1, GT_THREADS, 0, stream>>>(xyz1, pairs, cell_count, nullptr, nullptr);
-  DGR_CHECK(dgr_exclusive_scan_i32(A, cell_count, cell_start, ncell + 1, nullptr, stream));
-  if (ncell > 0) gt_grid_kernel<true><<<g1, GT_THREADS, 0, stream>>>(xyz1, pairs, cursor, cell_start, sorted);
+  DgrPointGridSet grid;
+  DGR_CHECK(dgr_point_grids_build(ctx, xyz1, hgrids.data(), npairs, radius, pin, "dgr_radius_pairs_batch", "batch", &grid, stream));
+  const dim3 g0((unsigned)dgr_ceil_div(max0, GT_THREADS), npairs);
   const double r2 = radius * radius;
-  gt_radius_kernel<false><<<g0, GT_THREADS, 0, stream>>>(xyz0, pairs, cell_start, sorted, r2, K, counts_out, nullptr, nullptr);
+  gt_radius_kernel<false><<<g0, GT_THREADS, 0, stream>>>(xyz0, pairs, grid.grids, grid.cell_start, grid.sorted, r2, K, counts_out,
+                                                        nullptr, nullptr);
   const int nsb = (int)dgr_ceil_div(n0_all, GT_SCAN_ROWS);
   int64_t *bsum, *row_off;
   DGR_ALLOC(bsum, A, int64_t, nsb);
   DGR_ALLOC(row_off, A, int64_t, n0_all + 1);
   gt_scan_sums_kernel<<<nsb, GT_THREADS, 0, stream>>>(counts_out, n0_all, bsum);
-  gt_scan_blocks_kernel<<<1, GT_THREADS, 0, stream>>>(bsum, nsb, totals + 1);
+  gt_scan_blocks_kernel<<<1, GT_THREADS, 0, stream>>>(bsum, nsb, total_pairs);
   DGR_LAUNCH_CHECK();
-  DGR_HIP_CHECK(hipMemcpyAsync(pin, totals + 1, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  DGR_HIP_CHECK(hipMemcpyAsync(pin, total_pairs, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
   DGR_CHECK(dgr_ctx_wait(ctx, stream));
   const int64_t total = landed[0];
   *total_out = total;
   if (!pairs_out) return DGR_OK;
   DGR_REQUIRE(capacity >= total, "dgr_radius_pairs_batch: capacity %lld below the %lld pairs of the batch",
               (long long)capacity, (long long)total);
-  gt_scan_final_kernel<<<nsb, GT_THREADS, 0, stream>>>(counts_out, n0_all, bsum, totals + 1, row_off);
-  gt_radius_kernel<true><<<g0, GT_THREADS, 0, stream>>>(xyz0, pairs, cell_start, sorted, r2, K, nullptr, row_off,
-                                                       reinterpret_cast<longlong2 *>(pairs_out));
+  gt_scan_final_kernel<<<nsb, GT_THREADS, 0, stream>>>(counts_out, n0_all, bsum, total_pairs, row_off);
+  gt_radius_kernel<true><<<g0, GT_THREADS, 0, stream>>>(xyz0, pairs, grid.grids, grid.cell_start, grid.sorted, r2, K, nullptr,
+                                                       row_off, reinterpret_cast<longlong2 *>(pairs_out));
   DGR_LAUNCH_CHECK();
   DGR_CHECK(dgr_ctx_wait(ctx, stream));   // like every entry point that returns host values, this one synchronises
   return DGR_OK;

@@ -5,7 +5,7 @@
 // restated from the published Open3D 0.17 algorithm (oracle/open3d_reg.py has the CPU restatement and the
 // deviations that make RANSAC reproducible: counter-based sampling, f32 consensus test without fma).
 // Everything is stream-ordered and free of host round trips until the final result copy.
-#include "dgr_internal.h"
+#include "pointgrid.h"
 #include "svd3.h"
 
 int dgr_icp_impl(dgr_ctx *ctx, const float *src, int64_t N0, const float *dst, int64_t N1, double max_dist,
@@ -39,7 +39,9 @@ __device__ inline void umeyama_from_sums(double n, const double *Sp, const doubl
 }
 
 // ================================================================================================
-// ICP
+// ICP.  Its target grid is NOT a DgrPointGrid (pointgrid.h lends the bounding-box helpers only): the edge starts at exactly
+// max_dist, the records are three doubles, the test is d2 <= best and a row is finite by its sum -- merging any of these
+// would change which cell a point lands in or what a tie returns, and with it register()'s bits.
 // ================================================================================================
 constexpr int ICP_THREADS = 256;
 constexpr int ICP_NSUM = 17;   // n, sum p (3), sum q (3), sum q p^T (9), sum d^2
@@ -53,14 +55,6 @@ struct IcpState {
   int32_t done, iters, have_prev, ncell;
   uint32_t bmin[3], bmax[3];   // ordered-uint bounding box of the target
 };
-
-__device__ __forceinline__ uint32_t ord_f32(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float unord_f32(uint32_t k) {
-  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
-}
 
 __global__ void icp_init_kernel(IcpState *st, const double *T_init) {
   if (threadIdx.x != 0) return;
@@ -76,12 +70,8 @@ __global__ void __launch_bounds__(ICP_THREADS)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
   if (i < n && isfinite(dst[i * 3] + dst[i * 3 + 1] + dst[i * 3 + 2]))   // non-finite target points take no part
-    for (int d = 0; d < 3; ++d) lo[d] = hi[d] = ord_f32(dst[i * 3 + d]);
-  for (int s = 32; s >= 1; s >>= 1)
-    for (int d = 0; d < 3; ++d) {
-      lo[d] = min(lo[d], (uint32_t)__shfl_xor((int)lo[d], s, 64));
-      hi[d] = max(hi[d], (uint32_t)__shfl_xor((int)hi[d], s, 64));
-    }
+    for (int d = 0; d < 3; ++d) lo[d] = hi[d] = dgr_ord_f32(dst[i * 3 + d]);
+  dgr_bbox_wave_reduce(lo, hi);
   if ((threadIdx.x & 63) == 0)
     for (int d = 0; d < 3; ++d) { atomicMin(&st->bmin[d], lo[d]); atomicMax(&st->bmax[d], hi[d]); }
 }
@@ -90,7 +80,7 @@ __global__ void __launch_bounds__(ICP_THREADS)
 __global__ void icp_layout_kernel(IcpState *st, double max_dist, int32_t cell_cap) {
   if (threadIdx.x != 0) return;
   double lo[3], hi[3];
-  for (int d = 0; d < 3; ++d) { lo[d] = (double)unord_f32(st->bmin[d]); hi[d] = (double)unord_f32(st->bmax[d]); }
+  for (int d = 0; d < 3; ++d) { lo[d] = (double)dgr_unord_f32(st->bmin[d]); hi[d] = (double)dgr_unord_f32(st->bmax[d]); }
   double cell = max_dist > 0.0 ? max_dist : 1.0;
   for (int tries = 0; tries < 64; ++tries) {
     double total = 1.0;
