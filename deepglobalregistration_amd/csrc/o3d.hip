@@ -28,7 +28,8 @@ __device__ inline void umeyama_from_sums(double n, const double *Sp, const doubl
   double mp[3], mq[3], sig[9];
   for (int d = 0; d < 3; ++d) { mp[d] = Sp[d] / n; mq[d] = Sq[d] / n; }
   for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) sig[i * 3 + j] = Sqp[i * 3 + j] / n - mq[i] * mp[j];
+    for (int j = 0; j < 3; ++j)   // one pair has no spread: exactly 0, not the rounding of a contracted multiply-add
+      sig[i * 3 + j] = n < 2.0 ? 0.0 : Sqp[i * 3 + j] / n - mq[i] * mp[j];
   double U[9], sv[3], V[9];
   svd3(sig, U, sv, V);
   const double sg = (det3(U) * det3(V) < 0.0) ? -1.0 : 1.0;
@@ -41,7 +42,11 @@ __device__ inline void umeyama_from_sums(double n, const double *Sp, const doubl
 // ================================================================================================
 // ICP.  Its target grid is NOT a DgrPointGrid (pointgrid.h lends the bounding-box helpers only): the edge starts at exactly
 // max_dist, the records are three doubles, the test is d2 <= best and a row is finite by its sum -- merging any of these
-// would change which cell a point lands in or what a tie returns, and with it register()'s bits.
+// would change which cell a point lands in, and with it register()'s bits.  Among target points at exactly the same
+// distance the lexicographically smallest (x, y, z) is the match: a function of the coordinates alone, not of the order
+// in which icp_fill_kernel's threads reach a cell.  The 17 sums are taken relative to the centre of the target's bounding
+// box (IcpState::org) and the translation is moved back afterwards, so that clouds far from the origin lose no digits to
+// sum q p^T / n - mu_q mu_p^T (tests/test_gpu_o3d_edges.py holds one step to a bound at 1000 units out).
 // ================================================================================================
 constexpr int ICP_THREADS = 256;
 constexpr int ICP_NSUM = 17;   // n, sum p (3), sum q (3), sum q p^T (9), sum d^2
@@ -51,6 +56,7 @@ struct IcpState {
   double upd[12];      // last update [R | t], applied by the next step
   double fitness, rmse, prev_fitness, prev_rmse;
   double gmin[3], cell;
+  double org[3];       // origin of the 17 sums: the centre of the target's bounding box
   int32_t gdim[3];
   int32_t done, iters, have_prev, ncell;
   uint32_t bmin[3], bmax[3];   // ordered-uint bounding box of the target
@@ -91,6 +97,7 @@ __global__ void icp_layout_kernel(IcpState *st, double max_dist, int32_t cell_ca
   int64_t total = 1;
   for (int d = 0; d < 3; ++d) {
     st->gmin[d] = lo[d];
+    st->org[d] = 0.5 * (lo[d] + hi[d]);
     st->gdim[d] = (int32_t)(floor((hi[d] - lo[d]) / cell) + 1.0);
     total *= st->gdim[d];
   }
@@ -166,7 +173,11 @@ __global__ void __launch_bounds__(ICP_THREADS)
                          ez = sorted[(int64_t)p * 3 + 2] - pz;
             const double d2 = ex * ex + ey * ey + ez * ez;
             if (d2 <= best) {   // radius test and running minimum in one
-              if (d2 < best || !found) { q[0] = sorted[(int64_t)p * 3]; q[1] = sorted[(int64_t)p * 3 + 1]; q[2] = sorted[(int64_t)p * 3 + 2]; }
+              const double c0 = sorted[(int64_t)p * 3], c1 = sorted[(int64_t)p * 3 + 1], c2 = sorted[(int64_t)p * 3 + 2];
+              // equal d2: the lexicographically smallest (x, y, z) -- the order inside a cell is the arrival order of
+              // icp_fill_kernel's threads and must not decide
+              const bool lex = c0 < q[0] || (c0 == q[0] && (c1 < q[1] || (c1 == q[1] && c2 < q[2])));
+              if (d2 < best || !found || lex) { q[0] = c0; q[1] = c1; q[2] = c2; }
               best = d2;
               found = true;
             }
@@ -175,12 +186,16 @@ __global__ void __launch_bounds__(ICP_THREADS)
       }
     }
     if (found) {
+      // sums relative to the centre of the target's box: a matched pair lies within the box (+ max_dist), so the raw
+      // second moments stay of the size of the box, however far from the origin the clouds are
+      const double pv[3] = {px - st->org[0], py - st->org[1], pz - st->org[2]};
+      const double qv[3] = {q[0] - st->org[0], q[1] - st->org[1], q[2] - st->org[2]};
       s[0] = 1.0;
-      s[1] = px; s[2] = py; s[3] = pz;
-      s[4] = q[0]; s[5] = q[1]; s[6] = q[2];
-      const double pv[3] = {px, py, pz};
-      for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) s[7 + a * 3 + b] = q[a] * pv[b];
+      for (int a = 0; a < 3; ++a) {
+        s[1 + a] = pv[a];
+        s[4 + a] = qv[a];
+        for (int b = 0; b < 3; ++b) s[7 + a * 3 + b] = qv[a] * pv[b];
+      }
       s[16] = best;
     }
   }
@@ -232,6 +247,9 @@ __global__ void __launch_bounds__(ICP_THREADS)
   }
   double R[9], t[3];
   umeyama_from_sums(n, S + 1, S + 4, S + 7, R, t);
+  // the sums are relative to o = org (icp_step_kernel): q - o = R (p - o) + t'  ->  t = t' + o - R o
+  for (int i = 0; i < 3; ++i)
+    t[i] += st->org[i] - (R[i * 3] * st->org[0] + R[i * 3 + 1] * st->org[1] + R[i * 3 + 2] * st->org[2]);
   double Tn[16];
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 4; ++j)

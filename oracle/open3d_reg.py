@@ -109,6 +109,22 @@ def ransac_samples(seed, first, count, n_corr, ransac_n=4):
     return ((r.astype(np.uint64) * np.uint64(n_corr)) >> np.uint64(32)).astype(np.int64)
 
 
+def consensus(T, X32, Y32, thr2):
+    """Consensus of the hypothesis T [4,4] f64 over the f32 correspondences X32 -> Y32: (inlier count, sum of d2 over
+    the inliers accumulated sequentially in float32 in correspondence order, 0.0 without inliers).  The test and its
+    operation order are the docstring of `ransac_correspondence`."""
+    R = T[:3, :3].astype(np.float32)
+    t = T[:3, 3].astype(np.float32)
+    p0 = (R[0, 0] * X32[:, 0] + R[0, 1] * X32[:, 1]) + R[0, 2] * X32[:, 2] + t[0]
+    p1 = (R[1, 0] * X32[:, 0] + R[1, 1] * X32[:, 1]) + R[1, 2] * X32[:, 2] + t[1]
+    p2 = (R[2, 0] * X32[:, 0] + R[2, 1] * X32[:, 1]) + R[2, 2] * X32[:, 2] + t[2]
+    e0, e1, e2 = p0 - Y32[:, 0], p1 - Y32[:, 1], p2 - Y32[:, 2]
+    d2 = (e0 * e0 + e1 * e1) + e2 * e2
+    inl = d2 < thr2
+    c = int(inl.sum())
+    return c, (float(np.add.accumulate(d2[inl], dtype=np.float32)[-1]) if c else 0.0)
+
+
 def ransac_correspondence(X, Y, max_dist, num_hyp, seed=0, ransac_n=4, chunk=2048):
     """X, Y [N,3]: corresponding points (xyz0[idx0], xyz1[idx1]).  Returns (T [4,4] f64, best hypothesis
     index, inlier count, inlier rmse).  Consensus test in f32, fixed op order:
@@ -127,18 +143,9 @@ def ransac_correspondence(X, Y, max_dist, num_hyp, seed=0, ransac_n=4, chunk=204
         S = ransac_samples(seed, first, cnt, n, ransac_n)
         for h in range(cnt):
             T = umeyama(X64[S[h]], Y64[S[h]])
-            R = T[:3, :3].astype(np.float32)
-            t = T[:3, 3].astype(np.float32)
-            p0 = (R[0, 0] * X32[:, 0] + R[0, 1] * X32[:, 1]) + R[0, 2] * X32[:, 2] + t[0]
-            p1 = (R[1, 0] * X32[:, 0] + R[1, 1] * X32[:, 1]) + R[1, 2] * X32[:, 2] + t[1]
-            p2 = (R[2, 0] * X32[:, 0] + R[2, 1] * X32[:, 1]) + R[2, 2] * X32[:, 2] + t[2]
-            e0, e1, e2 = p0 - Y32[:, 0], p1 - Y32[:, 1], p2 - Y32[:, 2]
-            d2 = (e0 * e0 + e1 * e1) + e2 * e2
-            inl = d2 < thr2
-            c = int(inl.sum())
+            c, err = consensus(T, X32, Y32, thr2)
             if c < best[0]:
                 continue
-            err = float(np.add.accumulate(d2[inl], dtype=np.float32)[-1]) if c else 0.0
             if c > best[0] or err < best[1]:
                 best = (c, err, first + h, T)
     c, err, h, T = best
