@@ -68,6 +68,8 @@ SIGNATURES = {
     'dgr_maps_get_coords': (C.c_int, [vp, C.c_int, vp, C.c_int64, c_i64p]),
     'dgr_maps_get_kernel_map': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, C.c_int64,
                                           c_i64p, c_i64p]),
+    'dgr_maps_create_ex': (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(vp), vp]),
+    'dgr_maps_get_raw': (C.c_int, [vp, C.c_char_p, C.c_int, C.c_char_p, vp, C.c_int64, c_i64p, c_i64p]),
     'dgr_knn1_l2': (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp]),
     'dgr_knn1_l2_batch': (C.c_int, [vp, vp, c_i64p, vp, c_i64p, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     'dgr_knn_l2': (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

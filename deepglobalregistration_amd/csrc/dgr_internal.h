@@ -145,7 +145,9 @@ struct DgrNbrTable {
   // coordinates, bit d of the class = (coordinate d / tensor stride) & 1.  A fine row can only meet offsets whose
   // component d is 0 where its coordinate is even and +-1 where it is odd (the coarse voxel f - delta ts must lie on the
   // coarse lattice): 2^(odd dims) of the 27 offsets, the same ones for every row of a class (conv_up.hip).
-  // perm[c * cls_cap + i] = i-th row of class c (in no particular order), cls_count[c] = rows of class c.
+  // perm[c * cls_cap + i] = i-th row of class c in ASCENDING row order (cls_fill_kernel is a stable counting sort: the
+  // list is the same in every run; tests/test_gpu_maps_contract.py compares it), cls_count[c] = rows of class c;
+  // entries behind cls_count[c] are never written.
   int32_t *perm = nullptr, *cls_count = nullptr;
   int64_t cls_cap = 0;
 };

@@ -201,17 +201,38 @@ class NetHandle:
 
 # ----------------------------------------------------------------------------
 class Maps:
-    """Coordinate maps + kernel maps of one sparse tensor (inspection / parity tests)."""
+    """Coordinate maps + kernel maps of one sparse tensor (inspection / parity tests).  lean=True builds the object
+    exactly as a network forward builds its own maps (dgr_maps_create_ex, DGR_MAPS_LEAN)."""
 
-    def __init__(self, coords, D, conv1_kernel_size=3, device='cuda'):
+    def __init__(self, coords, D, conv1_kernel_size=3, device='cuda', lean=False):
         lib = _lib.load()
         self.device = torch.device(device)
         coords = _as(coords, torch.int32, self.device)
-        self.D = D
+        self.D, self.lean = D, bool(lean)
         h = vp()
-        check(lib.dgr_maps_create(get_ctx(self.device), ptr(coords), coords.shape[0], D, conv1_kernel_size,
-                                  C.byref(h), stream_ptr(self.device.index)))
+        if lean:
+            check(lib.dgr_maps_create_ex(get_ctx(self.device), ptr(coords), coords.shape[0], D, conv1_kernel_size, 1,
+                                         C.byref(h), stream_ptr(self.device.index)))
+        else:
+            check(lib.dgr_maps_create(get_ctx(self.device), ptr(coords), coords.shape[0], D, conv1_kernel_size,
+                                      C.byref(h), stream_ptr(self.device.index)))
         self.handle = h
+
+    def raw(self, kind, ts, field):
+        """One array of the object as it lies in device memory (dgr_maps_get_raw; test instrument): the library's own
+        row numbering, nothing translated or sorted.  kind 'level' | 'same' | 'conv1' | 'down' | 'nbr_same' | 'nbr_down'
+        | 'nbr_up'; scalars come back as int.  A field the build did not make raises ValueError."""
+        lib = _lib.load()
+        n, eb = C.c_int64(0), C.c_int64(0)
+        check(lib.dgr_maps_get_raw(self.handle, kind.encode(), ts, field.encode(), None, 0, C.byref(n), C.byref(eb)))
+        scalar = eb.value == 8
+        buf = np.empty(n.value, np.int64 if scalar else np.uint16 if eb.value == 2 else np.int32)
+        check(lib.dgr_maps_get_raw(self.handle, kind.encode(), ts, field.encode(), buf.ctypes.data, buf.nbytes,
+                                   C.byref(n), C.byref(eb)))
+        if scalar:
+            return int(buf[0])
+        shape = {'coords': (-1, self.D + 1), 'tile_desc': (-1, 4), 'nbr': (27, -1), 'perm': (8, -1)}.get(field)
+        return buf.reshape(shape) if shape else buf
 
     def __del__(self):
         try:

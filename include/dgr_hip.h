@@ -181,6 +181,29 @@ int dgr_maps_get_coords(dgr_maps *maps, int ts, int32_t *host_out, int64_t capac
 int dgr_maps_get_kernel_map(dgr_maps *maps, int kind, int ts, int32_t *rule_ptr, int64_t rule_cap,
                             int32_t *pair_in, int32_t *pair_out, int64_t pair_cap, int64_t *K,
                             int64_t *P);
+/* dgr_maps_create with build flags.  DGR_MAPS_LEAN: the object is built exactly as dgr_resunet_forward builds its own
+ * maps -- D = 3: the ten dense neighbour tables and nothing else (conv1 runs fused with its search); D = 6: the seven
+ * rule-major maps without pair_out on the same-stride maps and with pair_k on level 0 only.  flags = 0 is
+ * dgr_maps_create.  The translating getters above need pair_out: on a lean object they serve the coordinates, the
+ * neighbour tables and the strided maps only. */
+#define DGR_MAPS_LEAN 1
+int dgr_maps_create_ex(dgr_ctx *ctx, const int32_t *coords, int64_t N, int D, int conv1_kernel_size, int flags,
+                       dgr_maps **out, dgr_stream stream);
+/* Test instrument: ONE array of a built maps object copied to the host as it lies in memory -- the library's own row
+ * numbering, no translation through `canon`, no sorting.  Synchronises and copies, nothing else.
+ *   kind "level"                      field "coords" int32 [n, 1+D] | "canon" int32 [n] (renumbered levels only) |
+ *                                     "table" int32 [mask + 1] | scalars "n", "mask"
+ *   kind "same" | "conv1" | "down"    "rule_ptr", "tile_ptr" int32 [K+1] | "tile_desc" int32 [tile_ptr[K], 4] |
+ *                                     "pair_in", "pair_out", "out_pos", "in_pos" int32 [P] | "pair_k" uint16 [P] |
+ *                                     "out_ptr", "in_ptr" int32 [n_cap + 1] | scalars "pair_cap", "n_cap", "K"
+ *   kind "nbr_same" | "nbr_down" | "nbr_up"   "nbr" int32 [27, n_pad] | "perm" int32 [8, cls_cap] | "cls_count"
+ *                                     int32 [8] | scalars "n_pad", "cls_cap"
+ * (P = rule_ptr[K]; ts as in dgr_maps_get_kernel_map.)  Scalars come back as ONE int64.  *count / *elem_bytes are always
+ * returned; host_out may be NULL to query them.  A map, table or field this build did not make (pair_out of a lean
+ * same-stride map, in_pos of a same-stride map, canon of a level in the caller's order, ...) is DGR_EINVAL with a
+ * message, never an empty or stale array. */
+int dgr_maps_get_raw(dgr_maps *maps, const char *kind, int ts, const char *field, void *host_out,
+                     int64_t capacity_bytes, int64_t *count, int64_t *elem_bytes);
 
 /* ---- feature-space 1-NN: replaces core.knn.find_knn_gpu(F0, F1, nn_max_n, knn=1,
  * return_distance) (core/knn.py:23-74) incl. core.metrics.pdist (core/metrics.py:62-69).
