@@ -107,6 +107,97 @@ def write_ply(filename, xyz, binary=True):
                 f.write(f'{p[0]:.17g} {p[1]:.17g} {p[2]:.17g}\n'.encode())
 
 
+def write_ply_mesh(filename, xyz, triangles, normals=None, binary=True):
+    """A triangle mesh as PLY: vertices double x y z (then double nx ny nz with `normals`), faces as `property list uchar
+    int vertex_indices`.  The vertex block is what `write_ply` writes, so `read_ply` returns the same points."""
+    xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
+    tri = np.asarray(triangles).reshape(-1, 3)
+    if tri.dtype.kind not in 'iu':
+        raise ValueError(f'triangles must be integers, got {tri.dtype}')
+    if len(tri) and (tri.min() < 0 or tri.max() >= len(xyz)):
+        raise ValueError(f'a triangle names a vertex outside [0, {len(xyz)})')
+    cols = [xyz]
+    if normals is not None:
+        normals = np.asarray(normals, np.float64).reshape(-1, 3)
+        if normals.shape != xyz.shape:
+            raise ValueError(f'normals {normals.shape} do not match the vertices {xyz.shape}')
+        cols.append(normals)
+    rows = np.concatenate(cols, 1)
+    names = ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if normals is not None else [])
+    with open(filename, 'wb') as f:
+        f.write(b'ply\nformat ' + (b'binary_little_endian' if binary else b'ascii') + b' 1.0\n')
+        f.write(f'element vertex {len(xyz)}\n'.encode() + ''.join(f'property double {k}\n' for k in names).encode())
+        f.write(f'element face {len(tri)}\nproperty list uchar int vertex_indices\nend_header\n'.encode())
+        if binary:
+            f.write(rows.astype('<f8').tobytes())
+            faces = np.empty(len(tri), np.dtype([('n', 'u1'), ('v', '<i4', 3)]))
+            faces['n'], faces['v'] = 3, tri
+            f.write(faces.tobytes())
+        else:
+            for r in rows:
+                f.write((' '.join(f'{v:.17g}' for v in r) + '\n').encode())
+            for t in tri:
+                f.write(f'3 {t[0]} {t[1]} {t[2]}\n'.encode())
+
+
+def read_ply_mesh(filename):
+    """dict(xyz float64 [N,3], triangles int32 [T,3][, normals float64 [N,3]]) of an ASCII or binary PLY whose elements
+    are `vertex` (scalar properties) and then `face` (one list property of three indices per face)."""
+    with open(filename, 'rb') as f:
+        if f.readline().strip() != b'ply':
+            raise ValueError(f'{filename}: not a PLY file')
+        fmt, elements = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f'{filename}: unterminated PLY header')
+            tok = line.decode('ascii', 'replace').split()
+            if not tok or tok[0] in ('comment', 'obj_info'):
+                continue
+            if tok[0] == 'format':
+                fmt = tok[1]
+            elif tok[0] == 'element':
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == 'property':
+                elements[-1][2].append(tok[1:])
+            elif tok[0] == 'end_header':
+                break
+        if fmt not in ('ascii', 'binary_little_endian', 'binary_big_endian'):
+            raise ValueError(f'{filename}: unsupported PLY format {fmt}')
+        if [e[0] for e in elements[:2]] != ['vertex', 'face']:
+            raise ValueError(f'{filename}: expected the elements "vertex" and "face"')
+        (_, n, props), (_, nf, fprops) = elements[:2]
+        if any(p[0] == 'list' for p in props):
+            raise ValueError(f'{filename}: list properties on vertices are not supported')
+        if len(fprops) != 1 or fprops[0][0] != 'list':
+            raise ValueError(f'{filename}: a face must be one list property')
+        names = [p[1] for p in props]
+        if not all(k in names for k in 'xyz'):
+            raise ValueError(f'{filename}: vertex element has no x/y/z')
+        if fmt == 'ascii':
+            rows = [f.readline().split() for _ in range(n)]
+            data = np.array(rows, dtype=np.float64).reshape(n, len(names))
+            col = {k: data[:, i] for i, k in enumerate(names)}
+            faces = [f.readline().split() for _ in range(nf)]
+            if any(len(r) != 4 or r[0] != b'3' for r in faces):
+                raise ValueError(f'{filename}: only triangles are supported')
+            tri = np.array(faces, dtype=np.int64).reshape(nf, 4)[:, 1:].astype(np.int32)
+        else:
+            order = '<' if fmt == 'binary_little_endian' else '>'
+            dt = np.dtype([(p[1], order + _PLY_TYPES[p[0]]) for p in props])
+            data = np.frombuffer(f.read(dt.itemsize * n), dtype=dt, count=n)
+            col = {k: data[k].astype(np.float64) for k in names}
+            ft = np.dtype([('n', order + _PLY_TYPES[fprops[0][1]]), ('v', order + _PLY_TYPES[fprops[0][2]], 3)])
+            faces = np.frombuffer(f.read(ft.itemsize * nf), dtype=ft, count=nf)
+            if (faces['n'] != 3).any():
+                raise ValueError(f'{filename}: only triangles are supported')
+            tri = faces['v'].astype(np.int32).reshape(nf, 3)
+    out = {'xyz': np.stack([col[k] for k in 'xyz'], 1), 'triangles': tri}
+    if all(k in col for k in ('nx', 'ny', 'nz')):
+        out['normals'] = np.stack([col[k] for k in ('nx', 'ny', 'nz')], 1)
+    return out
+
+
 def load_cloud(filename):
     """xyz [N,3] from .ply / .bin (KITTI) / .npy / .npz (key 'pcd' like the reference's 3DMatch pairs, else
     'xyz' or the first array) / .txt."""

@@ -905,6 +905,77 @@ def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1
 
 
 # ----------------------------------------------------------------------------
+# triangle mesh and vertex normals of a fused TSDF volume (csrc/tsdfmesh.hip)
+TSDF_MESH_FIRST_VERTICES, TSDF_MESH_FIRST_TRIANGLES = 1 << 20, 1 << 21   # tsdf_mesh's first output arrays; it asks again when they are small
+
+
+def check_tsdf_mesh_args(blocks, tsdf, weight, voxel_length, block=16, min_weight=1):
+    """The arguments of `tsdf_mesh` checked on the host: (nb, voxel_length, block, min_weight).  ValueError for tensors that
+    are not on one GPU, a `blocks` that is not int32 [nb,3], a `tsdf` that is not float32 [nb, block^3], a `weight` that is
+    not int32 of `tsdf`'s shape, a `block` other than 8 or 16, a `voxel_length` that is not a positive finite number,
+    `min_weight` < 1, 5 nb block^3 >= 2^31.  Nothing touches the device (block coordinates are checked there)."""
+    def number(v, name):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(v) or v <= 0:
+            raise ValueError(f'{name} must be a positive finite number, got {v!r}')
+        return float(v)
+
+    def integer(v, name, ok, what):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not ok(v):
+            raise ValueError(f'{name} must be {what}, got {v!r}')
+        return int(v)
+    voxel_length = number(voxel_length, 'voxel_length')
+    block = integer(block, 'block', lambda v: v in (8, 16), '8 or 16')
+    min_weight = integer(min_weight, 'min_weight', lambda v: 1 <= v < 2 ** 31, 'an integer >= 1')
+    for t, name in ((blocks, 'blocks'), (tsdf, 'tsdf'), (weight, 'weight')):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f'{name} must be a tensor on the GPU')
+    if not (blocks.device == tsdf.device == weight.device):
+        raise ValueError('blocks, tsdf and weight must be on one device')
+    if blocks.dtype != torch.int32 or blocks.ndim != 2 or blocks.shape[1] != 3:
+        raise ValueError(f'blocks must be int32 [nb,3], got {blocks.dtype} {tuple(blocks.shape)}')
+    nb = int(blocks.shape[0])
+    if tsdf.dtype != torch.float32 or tuple(tsdf.shape) != (nb, block ** 3):
+        raise ValueError(f'tsdf must be float32 [{nb},{block ** 3}], got {tsdf.dtype} {tuple(tsdf.shape)}')
+    if weight.dtype != torch.int32 or tuple(weight.shape) != (nb, block ** 3):
+        raise ValueError(f'weight must be int32 [{nb},{block ** 3}], got {weight.dtype} {tuple(weight.shape)}')
+    if 5 * nb * block ** 3 >= 2 ** 31:
+        raise ValueError(f'{nb} blocks of {block}^3 voxels: 2^31 or more possible triangles')
+    return nb, voxel_length, block, min_weight
+
+
+def tsdf_mesh(blocks, tsdf, weight, voxel_length, block=16, min_weight=1, normals=True):
+    """Triangle mesh and vertex normals of a fused TSDF volume (dgr_tsdf_mesh; Open3D's extract_triangle_mesh in the
+    reference's util/integration.py).  blocks int32 [nb,3], tsdf float32 [nb, block^3], weight int32 [nb, block^3]: device
+    tensors as `tsdf_fragment(..., return_volume=True)` returns them, or a volume made by hand in that layout.
+    Returns a dict of device tensors: `xyz` float64 [P,3] -- the very points of `tsdf_fragment`, in its order --, `normal`
+    float64 [P,3] (unit, from negative to positive; absent without `normals`) and `triangles` int32 [T,3], wound so that
+    they face the positive side.  Two calls agree bit for bit."""
+    nb, voxel_length, block, min_weight = check_tsdf_mesh_args(blocks, tsdf, weight, voxel_length, block, min_weight)
+    lib = _lib.load()
+    dev = blocks.device
+    blocks, tsdf, weight = blocks.contiguous(), tsdf.contiguous(), weight.contiguous()
+    max_v, max_t = TSDF_MESH_FIRST_VERTICES, TSDF_MESH_FIRST_TRIANGLES
+    nv, nt = C.c_int64(0), C.c_int64(0)
+    while True:
+        xyz = torch.empty((max_v, 3), dtype=torch.float64, device=dev)
+        normal = torch.empty((max_v, 3), dtype=torch.float64, device=dev) if normals else None
+        tri = torch.empty((max_t, 3), dtype=torch.int32, device=dev)
+        rc = lib.dgr_tsdf_mesh(get_ctx(dev), ptr(blocks), nb, ptr(tsdf), ptr(weight), block, voxel_length, min_weight,
+                               ptr(xyz), ptr(normal), max_v, ptr(tri), max_t, C.byref(nv), C.byref(nt), stream_ptr(dev.index))
+        # the one recoverable failure: an output array too small -- the call says how much both need
+        if rc == _lib.DGR_ENOMEM and (nv.value > max_v or nt.value > max_t):
+            max_v, max_t = max(max_v, nv.value), max(max_t, nt.value)
+            continue
+        check(rc)
+        break
+    out = {'xyz': xyz[:nv.value], 'triangles': tri[:nt.value]}
+    if normals:
+        out['normal'] = normal[:nv.value]
+    return out
+
+
+# ----------------------------------------------------------------------------
 # pose-graph optimisation over scored pairs (csrc/posegraph.hip)
 PG_MAX_NODES = 128   # DGR_PG_MAX_NODES
 

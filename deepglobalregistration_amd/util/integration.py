@@ -1,16 +1,17 @@
 """Depth frames -> fragments (util/integration.py of the reference): every `n_frames_per_fragment` frames of a 3DMatch-style
 sequence are fused into one TSDF volume on the GPU (`ops.tsdf_fragment`) and the surface points are written as
 `fragment-N.ply`.  Colour is not integrated, so colour files are neither read nor required; the points are the vertices of
-the mesh the reference writes, without its triangles (the loaders read vertices only).
+the mesh the reference writes, without its triangles (the loaders read vertices only).  With `mesh` (`--mesh`) the file is
+that mesh: the same vertices in the same order, their normals and the triangles (`ops.tsdf_mesh`).
 
-    python -m deepglobalregistration_amd.util.integration DATASET OUTPUT
+    python -m deepglobalregistration_amd.util.integration DATASET OUTPUT [--mesh]
 """
 import argparse
 import os
 
 import numpy as np
 
-from ..eval.formats import read_png_gray, write_ply
+from ..eval.formats import read_png_gray, write_ply, write_ply_mesh
 
 
 def read_pose(pose_file):
@@ -38,10 +39,11 @@ def read_depth(depth_file):
 
 
 def integrate_frames_for_fragment(depth_files, pose_files, seq_path, intrinsic, fragment_id, n_frames_per_fragment,
-                                  voxel_length=0.008, sdf_trunc=0.04, relative_to_first=False, **tsdf_args):
+                                  voxel_length=0.008, sdf_trunc=0.04, relative_to_first=False, mesh=False, **tsdf_args):
     """The points (float64 [P,3] device tensor) of fragment `fragment_id`: frames [id n, (id + 1) n) of the sorted file
     lists, fused by `ops.tsdf_fragment` (further keyword arguments go to it).  `relative_to_first`: the fragment in the
-    frame of its first camera (every pose premultiplied by the inverse of the fragment's first)."""
+    frame of its first camera (every pose premultiplied by the inverse of the fragment's first).  With `mesh` the dict of
+    `ops.tsdf_mesh` on the fused volume instead: `xyz` (the same points), `normal`, `triangles`."""
     from .. import ops
     start = fragment_id * n_frames_per_fragment
     end = min(start + n_frames_per_fragment, len(pose_files))
@@ -51,7 +53,12 @@ def integrate_frames_for_fragment(depth_files, pose_files, seq_path, intrinsic, 
     pose = np.stack([read_pose(os.path.join(seq_path, pose_files[i])) for i in range(start, end)])
     if relative_to_first:
         pose = np.linalg.inv(pose[0]) @ pose
-    return ops.tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, **tsdf_args)
+    if not mesh:
+        return ops.tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, **tsdf_args)
+    tsdf_args = dict(tsdf_args, return_volume=True)
+    vol = ops.tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, **tsdf_args)
+    return ops.tsdf_mesh(vol['blocks'], vol['tsdf'], vol['weight'], voxel_length, block=tsdf_args.get('block', 16),
+                         min_weight=tsdf_args.get('min_weight', 1))
 
 
 def list_sequence(seq_path):
@@ -72,18 +79,22 @@ def list_sequence(seq_path):
 
 
 def process_seq(seq_path, output_path, n_frames_per_fragment=50, voxel_length=0.008, sdf_trunc=0.04,
-                relative_to_first=False, **tsdf_args):
+                relative_to_first=False, mesh=False, **tsdf_args):
     """Writes `fragment-{id}.ply` into `output_path` for every `n_frames_per_fragment` frames of the sequence (the last
-    fragment takes what is left).  Returns the files written."""
+    fragment takes what is left): the surface points, or with `mesh` the triangle mesh with vertex normals, whose vertices
+    are those points.  Returns the files written."""
     intrinsic, depth_files, pose_files = list_sequence(seq_path)
     n_fragments = (len(depth_files) + n_frames_per_fragment - 1) // n_frames_per_fragment
     os.makedirs(output_path, exist_ok=True)
     written = []
     for fragment_id in range(n_fragments):
-        xyz = integrate_frames_for_fragment(depth_files, pose_files, seq_path, intrinsic, fragment_id, n_frames_per_fragment,
-                                            voxel_length, sdf_trunc, relative_to_first, **tsdf_args)
+        out = integrate_frames_for_fragment(depth_files, pose_files, seq_path, intrinsic, fragment_id, n_frames_per_fragment,
+                                            voxel_length, sdf_trunc, relative_to_first, mesh, **tsdf_args)
         name = os.path.join(output_path, 'fragment-{}.ply'.format(fragment_id))
-        write_ply(name, xyz.cpu().numpy())
+        if mesh:
+            write_ply_mesh(name, out['xyz'].cpu().numpy(), out['triangles'].cpu().numpy(), out['normal'].cpu().numpy())
+        else:
+            write_ply(name, out.cpu().numpy())
         written.append(name)
     return written
 
@@ -95,12 +106,13 @@ def main(argv=None):
     parser.add_argument('--frames', type=int, default=50, help='frames per fragment')
     parser.add_argument('--voxel', type=float, default=0.008)
     parser.add_argument('--relative-to-first', action='store_true', help="fragments in their first camera's frame")
+    parser.add_argument('--mesh', action='store_true', help='write triangle meshes with vertex normals, not points only')
     args = parser.parse_args(argv)
     scene_name = os.path.basename(os.path.normpath(args.dataset))
     output_scene_path = os.path.join(args.output, scene_name)
     for seq in sorted(s for s in os.listdir(args.dataset) if s.startswith('seq')):
         files = process_seq(os.path.join(args.dataset, seq), os.path.join(output_scene_path, seq), args.frames, args.voxel,
-                            relative_to_first=args.relative_to_first)
+                            relative_to_first=args.relative_to_first, mesh=args.mesh)
         print(f'{seq}: {len(files)} fragments -> {os.path.join(output_scene_path, seq)}')
 
 

@@ -558,6 +558,43 @@ int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframes, int heig
                       int64_t max_points, int32_t *blocks_out, float *tsdf_out, int32_t *weight_out, int64_t max_blocks,
                       int64_t *n_blocks_out, int64_t *n_points_out, int64_t *kept_out, dgr_stream stream);
 
+/* Triangle mesh and vertex normals of a fused TSDF volume (csrc/tsdfmesh.hip): what the reference's util/integration.py gets
+ * from Open3D's volume.extract_triangle_mesh().  Open3D is absent here: triangulation and roundings below are this library's
+ * own statement, and tests/tsdf_mesh_ref.py is the same statement in numpy, compared bit for bit.
+ * blocks dev i32 [n_blocks,3] in any order, tsdf dev f32 and weight dev i32 [n_blocks, block^3] with l = (lz block + ly) block
+ * + lx: the volume dgr_tsdf_fragment returns, or one made by hand.  Voxel i is "usable" iff its block is in the list,
+ * weight >= min_weight and -0.98f <= tsdf < 0.98f.  float64 without fma, every step one correctly rounded operation.
+ *   vertices     exactly the points of dgr_tsdf_fragment: blocks in list order, voxels by l, axes a = 0, 1, 2; a vertex on
+ *                the edge (i0, a), i1 = i0 + e_a, iff both ends are usable and (f0 < 0) != (f1 < 0); r = |f0| / (|f0| + |f1|);
+ *                position (i0 + 0.5) voxel_length with + voxel_length r on axis a.  Vertex k of the mesh is point k of the
+ *                fragment; a vertex no triangle uses stays in the list
+ *   normals      F(j; i) = (double)tsdf[j] if voxel j exists and weight[j] >= min_weight, else (double)tsdf[i];
+ *                g(i)[e] = F(i + e_e; i) - F(i - e_e; i); n[e] = g(i0)[e] + r (g(i1)[e] - g(i0)[e]) with the very r of the
+ *                position; len = sqrt((n0^2 + n1^2) + n2^2); normal = n / len, (0, 0, 0) when len == 0.  It points from
+ *                negative to positive, the side the triangles face.  Non-finite tsdf values are outside the contract
+ *   cells        cell i has the corners i + ((c & 1), (c >> 1) & 1, (c >> 2) & 1), c = 0..7, and the place (block, l) of
+ *                voxel i; it is valid iff all eight corners are usable; configuration bit c set iff tsdf[corner c] < 0
+ *                (-0.0f is not negative).  Every sign-changing edge of a valid cell is a vertex
+ *   triangles    blocks in list order, cells by l, the triangles of the configuration in table order (csrc/mc_table.h,
+ *                generated by tools/gen_mc_table.py from the rule stated there), three vertex indices each.  Edge e = 4 a + j
+ *                of a cell lies along axis a, bit 0 of j the offset on the lower other axis, bit 1 on the higher; its
+ *                vertex is the one owned by the edge's low corner voxel, in up to seven other blocks.  (v1 - v0) x (v2 - v0)
+ *                points to the positive side; two cells that share a face cut it alike, so the mesh is watertight
+ * Outputs: xyz_out dev f64 [max_vertices,3], normal_out dev f64 [max_vertices,3] (NULL: not computed), tri_out dev i32
+ * [max_triangles,3]; *n_vertices_out, *n_triangles_out HOST: the call synchronises once, for both.  n_blocks = 0: zero
+ * vertices, zero triangles, DGR_OK.  No floating-point atomics, output positions come from scans: two runs agree bit for bit.
+ * DGR_ENOMEM: the workspace cannot be grown; more vertices than max_vertices or more triangles than max_triangles (nothing is
+ * written to either output; both out-parameters hold what is needed); 5 n_blocks block^3 >= 2^31.  The library never writes
+ * past a capacity.
+ * DGR_EINVAL before any device work: a NULL argument (normal_out may be NULL; blocks, tsdf, weight only with n_blocks = 0;
+ * xyz_out / tri_out only with a capacity of 0), n_blocks < 0, block not 8 or 16, min_weight < 1, voxel_length not positive and
+ * finite, a negative capacity.  DGR_EINVAL found on the device and reported at the synchronisation, before anything is written
+ * to an output: a block coordinate outside [-2^26, 2^26) (DGR_TSDF_BLOCK_LIMIT), a block that occurs twice in the list. */
+int dgr_tsdf_mesh(dgr_ctx *ctx, const int32_t *blocks, int64_t n_blocks, const float *tsdf, const int32_t *weight, int block,
+                  double voxel_length, int min_weight, double *xyz_out, double *normal_out, int64_t max_vertices,
+                  int32_t *tri_out, int64_t max_triangles, int64_t *n_vertices_out, int64_t *n_triangles_out,
+                  dgr_stream stream);
+
 /* ---- debug entry points (parity tests): the device functions of the registration kernel on their own.
  * ortho2rotation (core/registration.py:16-64) forward for n parameter rows p6 [n,6] -> R9_out [n,9] (row-major 3x3) and,
  * when grad_R9 [n,9] and grad_p6_out [n,6] are given, its backward (what autograd computes for sum(R * grad_R)).
