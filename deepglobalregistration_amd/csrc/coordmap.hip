@@ -6,6 +6,7 @@
 
 #include "dgr_internal.h"
 #include "hash.h"
+#include "scan.h"
 
 // ------------------------------------------------------------------------------------------
 // exclusive scan (int32): block-local scan + single-block scan of the block sums
@@ -14,59 +15,24 @@ constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_BLOCK = SCAN_THREADS * SCAN_ITEMS;
 
-__device__ __forceinline__ int block_exclusive_scan_256(int v, int *lds /*>=4 ints*/, int *total) {
-  // wave-level inclusive scan with DPP-free shuffles (wave64), then 4 wave totals through LDS
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    int y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) lds[wave] = x;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < SCAN_THREADS / 64; ++w) {
-    int s = lds[w];
-    if (w < wave) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + x - v;
-}
-
 // one workgroup, 1024 threads x 4 items per round with a running carry: ONE launch instead of three
 // for the many small scans of the map build (n <= a few 100 k), where launch boundaries dominate
 __global__ void __launch_bounds__(1024) scan_single_block(const int32_t *__restrict__ in, int64_t n,
                                                           int32_t *__restrict__ out, int32_t *total_out) {
-  __shared__ int wsum[16];
-  __shared__ int carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
+  __shared__ int lds[16];
+  int carry = 0;
   for (int64_t base = 0; base < n; base += 4096) {
     const int64_t i0 = base + (int64_t)threadIdx.x * 4;
     int v[4], s = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { v[j] = (i0 + j < n) ? in[i0 + j] : 0; s += v[j]; }
-    int x = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int wbase = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) { const int t = wsum[w]; if (w < wave) wbase += t; tot += t; }
-    int ex = carry_s + wbase + x - s;
+    int tot;
+    int ex = carry + dgr_block_exclusive<int, 1024>(s, lds, &tot);
 #pragma unroll
     for (int j = 0; j < 4; ++j) { if (i0 + j < n) out[i0 + j] = ex; ex += v[j]; }
-    __syncthreads();
-    if (threadIdx.x == 0) carry_s += tot;
-    __syncthreads();
+    carry += tot;
   }
-  if (threadIdx.x == 0 && total_out) *total_out = carry_s;
+  if (threadIdx.x == 0 && total_out) *total_out = carry;
 }
 
 // Up to DGR_SCAN_MAX independent scans in the SAME three launches (blockIdx.y = array): the map builders need two or
@@ -91,7 +57,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_block_sums_multi(ScanJobs j
   for (int i = 0; i < SCAN_ITEMS; ++i)
     if (base + i < n) s += in[base + i];
   int tot;
-  block_exclusive_scan_256(s, lds, &tot);
+  dgr_block_exclusive<int, SCAN_THREADS>(s, lds, &tot);
   if (threadIdx.x == 0) j.sums[a][blockIdx.x] = tot;
 }
 
@@ -105,7 +71,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_sums_serial_multi(ScanJobs 
     int i = b0 + threadIdx.x;
     int v = i < nblocks ? sums[i] : 0;
     int tot;
-    int ex = block_exclusive_scan_256(v, lds, &tot);
+    int ex = dgr_block_exclusive<int, SCAN_THREADS>(v, lds, &tot);
     if (i < nblocks) sums[i] = carry + ex;
     carry += tot;
   }
@@ -128,7 +94,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_final_multi(ScanJobs j) {
     s += v[i];
   }
   int tot;
-  int ex = block_exclusive_scan_256(s, lds, &tot) + j.sums[a][blockIdx.x];
+  int ex = dgr_block_exclusive<int, SCAN_THREADS>(s, lds, &tot) + j.sums[a][blockIdx.x];
 #pragma unroll
   for (int i = 0; i < SCAN_ITEMS; ++i) {
     if (base + i < n) out[base + i] = ex;
@@ -177,50 +143,39 @@ int dgr_exclusive_scan_i32(DgrArena &arena, const int32_t *in, int32_t *out, int
 // first-occurrence unique over int32 key rows
 // ------------------------------------------------------------------------------------------
 // table[slot] ends up holding the SMALLEST row index among the rows that share a key, so the
-// surviving row ("first occurrence") does not depend on thread scheduling.
+// surviving row ("first occurrence") does not depend on thread scheduling (dgr_insert_first, hash.h).
+// Both kernels serve every table of 3-, 4- and 7-int keys.  state (nullable): a row whose entry is DGR_ROW_DROPPED takes
+// no part.  The keys must come from a kernel that has finished.
 template <int NC>
 __global__ void unique_insert(const int32_t *__restrict__ keys, const int32_t *n_dev, int64_t n_cap,
-                              int32_t *table, uint32_t mask) {
+                              const int32_t *__restrict__ state, int32_t *table, uint32_t mask) {
   int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t n = n_dev ? *n_dev : n_cap;
-  if (r >= n) return;
-  int32_t me[NC];
-#pragma unroll
-  for (int d = 0; d < NC; ++d) me[d] = keys[r * NC + d];
-  uint32_t slot = dgr_hash_row<NC>(me) & mask;
-  while (true) {
-    int cur = __hip_atomic_load(&table[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == DGR_EMPTY) {
-      int old = atomicCAS(&table[slot], DGR_EMPTY, (int)r);
-      if (old == DGR_EMPTY) return;
-      cur = old;
-    }
-    if (dgr_rows_equal<NC>(keys + (int64_t)cur * NC, me)) {
-      atomicMin(&table[slot], (int)r);
-      return;
-    }
-    slot = (slot + 1) & mask;
-  }
+  if (r >= n || (state && state[r] == DGR_ROW_DROPPED)) return;
+  dgr_insert_first<NC>(table, mask, keys, (int)r);
 }
 
+// first_flag[r] = "r is the row the table holds for its key" (0 for a dropped row and behind *n_dev); held (nullable): that
+// row, for the rows that take part -- it may be the same array as state, which is why neither is __restrict__; dup_flag
+// (nullable) is raised by a row that takes part and is not the first of its key.
 template <int NC>
-__global__ void unique_flag(const int32_t *__restrict__ keys, const int32_t *n_dev, int64_t n_cap,
-                            const int32_t *__restrict__ table, uint32_t mask,
-                            int32_t *__restrict__ first_flag, int32_t *dup_flag) {
+__global__ void unique_flag(const int32_t *__restrict__ keys, const int32_t *n_dev, int64_t n_cap, const int32_t *state,
+                            const int32_t *__restrict__ table, uint32_t mask, int32_t *__restrict__ first_flag,
+                            int32_t *held, int32_t *dup_flag) {
   int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_cap) return;
   int64_t n = n_dev ? *n_dev : n_cap;
-  if (r >= n) {
-    if (first_flag) first_flag[r] = 0;
-    return;
-  }
-  int32_t me[NC];
+  int first = 0;
+  if (r < n && !(state && state[r] == DGR_ROW_DROPPED)) {
+    int32_t me[NC];
 #pragma unroll
-  for (int d = 0; d < NC; ++d) me[d] = keys[r * NC + d];
-  int v = dgr_lookup<NC>(table, mask, keys, me);
-  int first = (v == (int)r) ? 1 : 0;
+    for (int d = 0; d < NC; ++d) me[d] = keys[r * NC + d];
+    int v = dgr_lookup<NC>(table, mask, keys, me);
+    if (held) held[r] = v;
+    first = (v == (int)r) ? 1 : 0;
+    if (!first && dup_flag) *dup_flag = 1;
+  }
   if (first_flag) first_flag[r] = first;
-  if (!first && dup_flag) *dup_flag = 1;
 }
 
 template <int NC>
@@ -260,34 +215,23 @@ static inline int grid_for(int64_t n, int threads = 256) { return (int)dgr_ceil_
 // keys [n,nc] -> table (row index of the surviving row per key), first_flag, rank (exclusive scan
 // of first_flag), n_unique.  All device-side; n may be a device count (n_dev) bounded by n_cap.
 template <int NC>
-static int unique_rows_t(DgrArena &arena, const int32_t *keys, const int32_t *n_dev, int64_t n_cap,
-                         int32_t *first_flag, int32_t *rank, int32_t *n_unique_dev,
+static int unique_rows_t(DgrArena &arena, const int32_t *keys, const int32_t *n_dev, int64_t n_cap, const int32_t *state,
+                         int32_t *held, int32_t *first_flag, int32_t *rank, int32_t *n_unique_dev,
                          int32_t **table_out, uint32_t *mask_out, hipStream_t stream) {
-  uint32_t cap = dgr_next_pow2((uint64_t)(2 * n_cap > 64 ? 2 * n_cap : 64));
-  int32_t *table;
-  DGR_ALLOC(table, arena, int32_t, cap);
-  DGR_HIP_CHECK(hipMemsetAsync(table, 0xff, (size_t)cap * sizeof(int32_t), stream));
-  unique_insert<NC><<<grid_for(n_cap), 256, 0, stream>>>(keys, n_dev, n_cap, table, cap - 1);
-  unique_flag<NC><<<grid_for(n_cap), 256, 0, stream>>>(keys, n_dev, n_cap, table, cap - 1, first_flag,
-                                                      nullptr);
+  DGR_CHECK(dgr_table_make(arena, n_cap, table_out, mask_out, stream));
+  unique_insert<NC><<<grid_for(n_cap), 256, 0, stream>>>(keys, n_dev, n_cap, state, *table_out, *mask_out);
+  unique_flag<NC><<<grid_for(n_cap), 256, 0, stream>>>(keys, n_dev, n_cap, state, *table_out, *mask_out, first_flag,
+                                                      held, nullptr);
   DGR_LAUNCH_CHECK();
-  DGR_CHECK(dgr_exclusive_scan_i32(arena, first_flag, rank, n_cap, n_unique_dev, stream));
-  *table_out = table;
-  *mask_out = cap - 1;
-  return DGR_OK;
+  return dgr_exclusive_scan_i32(arena, first_flag, rank, n_cap, n_unique_dev, stream);
 }
 
-int dgr_unique_rows(DgrArena &arena, const int32_t *keys, int64_t n, int nc, int32_t *first_flag,
-                    int32_t *rank, int32_t *n_unique_dev, int32_t **table_out, uint32_t *mask_out,
+int dgr_unique_rows(DgrArena &arena, const int32_t *keys, int64_t n, int nc, const int32_t *state, int32_t *held,
+                    int32_t *first_flag, int32_t *rank, int32_t *n_unique_dev, int32_t **table_out, uint32_t *mask_out,
                     hipStream_t stream) {
-  if (nc == 4)
-    return unique_rows_t<4>(arena, keys, nullptr, n, first_flag, rank, n_unique_dev, table_out,
-                            mask_out, stream);
-  if (nc == 7)
-    return unique_rows_t<7>(arena, keys, nullptr, n, first_flag, rank, n_unique_dev, table_out,
-                            mask_out, stream);
-  dgr_set_error("unsupported coordinate width %d", nc);
-  return DGR_EINVAL;
+  auto run = nc == 3 ? unique_rows_t<3> : nc == 4 ? unique_rows_t<4> : nc == 7 ? unique_rows_t<7> : nullptr;
+  DGR_REQUIRE(run, "unsupported key width %d", nc);
+  return run(arena, keys, nullptr, n, state, held, first_flag, rank, n_unique_dev, table_out, mask_out, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -304,16 +248,11 @@ static int build_coord_maps_t(DgrArena &arena, const int32_t *coords, int64_t N,
   DGR_ALLOC(c1.n_dev, arena, int32_t, 1);
   int32_t n32 = (int32_t)N;
   DGR_HIP_CHECK(hipMemcpyAsync(c1.n_dev, &n32, sizeof(int32_t), hipMemcpyHostToDevice, stream));
-  {
-    uint32_t cap = dgr_next_pow2((uint64_t)(2 * N > 64 ? 2 * N : 64));
-    DGR_ALLOC(c1.table, arena, int32_t, cap);
-    c1.table_mask = cap - 1;
-    DGR_HIP_CHECK(hipMemsetAsync(c1.table, 0xff, (size_t)cap * sizeof(int32_t), stream));
-    unique_insert<NC><<<grid_for(N), 256, 0, stream>>>(coords, nullptr, N, c1.table, cap - 1);
-    unique_flag<NC><<<grid_for(N), 256, 0, stream>>>(coords, nullptr, N, c1.table, cap - 1, nullptr,
-                                                    ms->overflow);
-    DGR_LAUNCH_CHECK();
-  }
+  DGR_CHECK(dgr_table_make(arena, N, &c1.table, &c1.table_mask, stream));
+  unique_insert<NC><<<grid_for(N), 256, 0, stream>>>(coords, nullptr, N, nullptr, c1.table, c1.table_mask);
+  unique_flag<NC><<<grid_for(N), 256, 0, stream>>>(coords, nullptr, N, nullptr, c1.table, c1.table_mask, nullptr, nullptr,
+                                                  ms->overflow);
+  DGR_LAUNCH_CHECK();
   // ts = 2,4,8: unique(floor(c / ts) * ts), first-occurrence order
   for (int l = 1; l < 4; ++l) {
     DgrCoordMap &p = ms->cm[l - 1];
@@ -327,7 +266,7 @@ static int build_coord_maps_t(DgrArena &arena, const int32_t *coords, int64_t N,
     DGR_ALLOC(c.coords, arena, int32_t, c.n_cap * NC);
     DGR_ALLOC(c.n_dev, arena, int32_t, 1);
     stride_keys<NC><<<grid_for(p.n_cap), 256, 0, stream>>>(p.coords, p.n_dev, c.ts, keys);
-    DGR_CHECK(unique_rows_t<NC>(arena, keys, p.n_dev, p.n_cap, flag, rank, c.n_dev, &c.table,
+    DGR_CHECK(unique_rows_t<NC>(arena, keys, p.n_dev, p.n_cap, nullptr, nullptr, flag, rank, c.n_dev, &c.table,
                                 &c.table_mask, stream));
     unique_compact<NC><<<grid_for(p.n_cap), 256, 0, stream>>>(keys, p.n_dev, p.n_cap, flag, rank,
                                                              c.coords, nullptr);
@@ -438,11 +377,11 @@ int dgr_build_half_buckets(DgrArena &arena, DgrCoordMap *cm, DgrHalfBuckets *hb,
                            hipStream_t stream) {
   DGR_REQUIRE(levels >= 1 && levels <= 4 && renumber_from >= 1, "half buckets: %d levels", levels);
   int32_t *keys[4], *flag[4], *rank[4], *nb_dev[4], *row_bucket[4], *counts[4], *cursor[4];
-  uint32_t cap[4];
+  uint64_t cap[4];
   size_t table_words = 0, count_words = 0;
   for (int l = 0; l < levels; ++l) {
     const int64_t n = cm[l].n_cap;
-    cap[l] = dgr_next_pow2((uint64_t)(2 * n > 64 ? 2 * n : 64));
+    cap[l] = dgr_table_slots(n);
     table_words += cap[l];
     count_words += 2 * (size_t)(n + 1);
   }
@@ -454,7 +393,7 @@ int dgr_build_half_buckets(DgrArena &arena, DgrCoordMap *cm, DgrHalfBuckets *hb,
   for (int l = 0; l < levels; ++l) {
     const int64_t n = cm[l].n_cap;
     hb[l].table = tables; tables += cap[l];
-    hb[l].mask = cap[l] - 1;
+    hb[l].mask = (uint32_t)(cap[l] - 1);
     counts[l] = cnts; cursor[l] = cnts + (n + 1); cnts += 2 * (n + 1);
     DGR_ALLOC(keys[l], arena, int32_t, n * 4);
     DGR_ALLOC(flag[l], arena, int32_t, n);
@@ -469,8 +408,9 @@ int dgr_build_half_buckets(DgrArena &arena, DgrCoordMap *cm, DgrHalfBuckets *hb,
   for (int l = 0; l < levels; ++l) {
     const int64_t n = cm[l].n_cap;
     half_keys_kernel<<<grid_for(n), 256, 0, stream>>>(cm[l].coords, cm[l].n_dev, keys[l]);
-    unique_insert<4><<<grid_for(n), 256, 0, stream>>>(keys[l], cm[l].n_dev, n, hb[l].table, hb[l].mask);
-    unique_flag<4><<<grid_for(n), 256, 0, stream>>>(keys[l], cm[l].n_dev, n, hb[l].table, hb[l].mask, flag[l], nullptr);
+    unique_insert<4><<<grid_for(n), 256, 0, stream>>>(keys[l], cm[l].n_dev, n, nullptr, hb[l].table, hb[l].mask);
+    unique_flag<4><<<grid_for(n), 256, 0, stream>>>(keys[l], cm[l].n_dev, n, nullptr, hb[l].table, hb[l].mask, flag[l], nullptr,
+                                                    nullptr);
   }
   DGR_LAUNCH_CHECK();
   {
@@ -577,7 +517,7 @@ extern "C" int dgr_voxelize(dgr_ctx *ctx, const void *xyz, int is_f64, int64_t M
   else
     voxel_keys<float><<<grid_for(M), 256, 0, stream>>>((const float *)xyz, M, 0.f, (float)voxel_size,
                                                       batch_index, keys);
-  DGR_CHECK(unique_rows_t<4>(A, keys, nullptr, M, flag, rank, n_dev, &table, &mask, stream));
+  DGR_CHECK(dgr_unique_rows(A, keys, M, 4, nullptr, nullptr, flag, rank, n_dev, &table, &mask, stream));
   unique_compact<4><<<grid_for(M), 256, 0, stream>>>(keys, nullptr, M, flag, rank, coords_out, sel_out);
   if (xyz_out) {
     if (is_f64)

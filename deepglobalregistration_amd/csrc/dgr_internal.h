@@ -177,9 +177,14 @@ int dgr_conv1_probe(DgrArena &arena, const DgrCoordMap &cm, int ks, const float 
                     const float *w_tiled, const float *shift, float *out, int out_ld, int32_t *pair_count,
                     hipStream_t stream, const float *w_compact = nullptr, const char **kernel_name = nullptr,
                     uint32_t *out_amax = nullptr);
-// voxelise helper (coordmap.hip)
-int dgr_unique_rows(DgrArena &arena, const int32_t *keys, int64_t n, int nc, int32_t *first_flag,
-                    int32_t *rank, int32_t *n_unique_dev, int32_t **table_out, uint32_t *mask_out,
+// per-row state for the optional `state` array of dgr_unique_rows: a row that takes no part / one whose row is not known yet
+constexpr int32_t DGR_ROW_DROPPED = -1, DGR_ROW_PENDING = -2;
+// First-occurrence unique over n int32 key rows of nc = 3, 4 or 7 ints (coordmap.hip): makes the table (hash.h; a slot holds
+// the smallest row of its key), first_flag[r] = "r is that row", rank = exclusive scan of the flags, *n_unique_dev = keys.
+// state (nullable): rows with state[r] == DGR_ROW_DROPPED are skipped and get flag 0.  held (nullable): held[r] = the row
+// the table holds for r's key, written for the rows that take part only; it may be the same array as `state`.
+int dgr_unique_rows(DgrArena &arena, const int32_t *keys, int64_t n, int nc, const int32_t *state, int32_t *held,
+                    int32_t *first_flag, int32_t *rank, int32_t *n_unique_dev, int32_t **table_out, uint32_t *mask_out,
                     hipStream_t stream);
 int dgr_exclusive_scan_i32(DgrArena &arena, const int32_t *in, int32_t *out, int64_t n,
                            int32_t *total_out, hipStream_t stream);
@@ -384,8 +389,3 @@ struct DgrRegResult {  // device-side result record of the registration kernel
   int32_t pad;
 };
 static inline int64_t dgr_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline uint32_t dgr_next_pow2(uint64_t v) {
-  uint32_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}

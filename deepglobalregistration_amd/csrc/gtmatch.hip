@@ -8,7 +8,9 @@
 // distances are ordered by the smaller index here (FLANN leaves them in tree order), which makes the list a function of
 // the input alone.  The transformation and the distances are float64 on the f32 points widened exactly, in a fixed
 // operation order without fma, so that a host restatement (tests, tests/golden/make_golden_gt_match.py) gets the same bits.
+#include "hash.h"
 #include "pointgrid.h"
+#include "scan.h"
 
 #include <cmath>
 #include <cstring>
@@ -59,38 +61,23 @@ __global__ void __launch_bounds__(GT_THREADS)
 // ---- exclusive scan of the int32 row counts into int64 offsets [n + 1] (the total can pass 2^31) ---------------------
 constexpr int GT_SCAN_ROWS = 1024;   // rows per block: 256 threads x 4 consecutive rows
 
-__device__ __forceinline__ int64_t gt_block_exclusive(int64_t v, int64_t *total) {   // exclusive prefix over the block
-  __shared__ int64_t wsum[GT_THREADS / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int64_t inc = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();   // (wsum of an earlier call has been read)
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  int64_t before = 0, all = 0;
-  for (int k = 0; k < GT_THREADS / 64; ++k) { if (k < w) before += wsum[k]; all += wsum[k]; }
-  *total = all;
-  return before + inc - v;
-}
-
 __global__ void __launch_bounds__(GT_THREADS) gt_scan_sums_kernel(const int32_t *__restrict__ counts, int64_t n, int64_t *bsum) {
   const int64_t r0 = (int64_t)blockIdx.x * GT_SCAN_ROWS + threadIdx.x * 4;
   int64_t v = 0;
   for (int k = 0; k < 4; ++k) v += (r0 + k < n) ? counts[r0 + k] : 0;
+  __shared__ int64_t lds[GT_THREADS / 64];
   int64_t total;
-  gt_block_exclusive(v, &total);
+  dgr_block_exclusive<int64_t, GT_THREADS>(v, lds, &total);
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 __global__ void __launch_bounds__(GT_THREADS) gt_scan_blocks_kernel(int64_t *bsum, int nblocks, int64_t *total_out) {
+  __shared__ int64_t lds[GT_THREADS / 64];
   int64_t carry = 0;
   for (int b0 = 0; b0 < nblocks; b0 += GT_THREADS) {
     const int b = b0 + threadIdx.x;
     const int64_t v = b < nblocks ? bsum[b] : 0;
     int64_t total;
-    const int64_t ex = gt_block_exclusive(v, &total);
+    const int64_t ex = dgr_block_exclusive<int64_t, GT_THREADS>(v, lds, &total);
     if (b < nblocks) bsum[b] = carry + ex;
     carry += total;
   }
@@ -103,8 +90,9 @@ __global__ void __launch_bounds__(GT_THREADS)
   int32_t c[4];
   int64_t v = 0;
   for (int k = 0; k < 4; ++k) { c[k] = (r0 + k < n) ? counts[r0 + k] : 0; v += c[k]; }
+  __shared__ int64_t lds[GT_THREADS / 64];
   int64_t unused;
-  int64_t at = bsum[blockIdx.x] + gt_block_exclusive(v, &unused);
+  int64_t at = bsum[blockIdx.x] + dgr_block_exclusive<int64_t, GT_THREADS>(v, lds, &unused);
   for (int k = 0; k < 4; ++k) {
     if (r0 + k < n) row_off[r0 + k] = at;
     at += c[k];
@@ -285,8 +273,7 @@ extern "C" int dgr_pairs_isin_batch(dgr_ctx *ctx, const int64_t *pos, const int6
   int64_t slots = 0;
   for (int p = 0; p < npairs; ++p) {
     const int64_t np = pos_off[p + 1] - pos_off[p];
-    uint64_t cap = 64;
-    while (cap < (uint64_t)(2 * np)) cap <<= 1;
+    const uint64_t cap = dgr_table_slots(np, 1ull << 62);
     host[p] = GtSet{pos_off[p], pred_off[p], M_per_pair[p], slots, cap - 1};
     slots += (int64_t)cap;
   }

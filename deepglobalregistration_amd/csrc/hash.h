@@ -1,4 +1,5 @@
-// Device-side coordinate hashing shared by coordmap.hip and kmap.hip.
+// Coordinate hashing shared by every voxel table of the library (coordmap.hip, kmap.hip, conv.hip, voxelmean.hip,
+// tsdf.hip, tsdfmesh.hip): the hash, the look-ups, the ONE probe-and-claim loop and the host helper that sizes a table.
 // COO coordinates are int32 rows [batch, x_0 .. x_{D-1}] (NC = 1 + D ints).  The hash table is
 // open addressing with linear probing; entries are row indices (-1 = empty) into the coordinate
 // array that owns the keys, so a probe is: 4-byte table read (L2-resident: 2 x N entries) and,
@@ -7,7 +8,29 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dgr_internal.h"
+
 #define DGR_EMPTY (-1)
+
+// Slots of the table of n rows: a power of two >= max(64, 2 n), at most 2^31 (the most a 32-bit mask addresses).  Up to
+// n = 2^30 rows the load is at most 1/2; beyond, up to the 2^31 - 1 rows an int32 row index can name, at least one slot
+// stays empty.  Either way every probe loop below meets an empty slot or its key and ends.
+// (gtmatch.hip's sets of 64-bit keys are addressed with a 64-bit mask and pass a higher limit.)
+static inline uint64_t dgr_table_slots(int64_t n, uint64_t max_slots = 1ull << 31) {
+  uint64_t cap = 64;
+  while (cap < 2 * (uint64_t)n && cap < max_slots) cap <<= 1;
+  return cap;
+}
+
+// a cleared table for n rows (n < 2^31), from the arena
+static inline int dgr_table_make(DgrArena &arena, int64_t n, int32_t **table_out, uint32_t *mask_out, hipStream_t stream) {
+  DGR_REQUIRE(n >= 0 && n < (1ll << 31), "hash table: %lld rows", (long long)n);
+  const uint64_t cap = dgr_table_slots(n);
+  DGR_ALLOC(*table_out, arena, int32_t, cap);
+  *mask_out = (uint32_t)(cap - 1);
+  DGR_HIP_CHECK(hipMemsetAsync(*table_out, 0xff, (size_t)cap * sizeof(int32_t), stream));
+  return DGR_OK;
+}
 
 __device__ __forceinline__ uint32_t dgr_rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
@@ -38,6 +61,40 @@ __device__ __forceinline__ bool dgr_rows_equal(const int32_t *a, const int32_t *
 #pragma unroll
   for (int d = 0; d < NC; ++d) eq &= (a[d] == b[d]);
   return eq;
+}
+
+// The probe-and-claim loop: walks from the hash of row r's key to the first slot that is empty or holds a row with the
+// same key.  Returns DGR_EMPTY if r took an empty slot, else the row that was seen holding the slot; *slot_out = the slot.
+// Ends because the table has an empty slot (dgr_table_slots); every key it compares against must have been written by a
+// kernel that has finished.
+template <int NC>
+__device__ __forceinline__ int dgr_claim(int32_t *table, uint32_t mask, const int32_t *__restrict__ keys, int r,
+                                         uint32_t *slot_out) {
+  int32_t me[NC];
+#pragma unroll
+  for (int d = 0; d < NC; ++d) me[d] = keys[(int64_t)r * NC + d];
+  uint32_t slot = dgr_hash_row<NC>(me) & mask;
+  int cur;
+  while (true) {
+    cur = __hip_atomic_load(&table[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == DGR_EMPTY) {
+      cur = atomicCAS(&table[slot], DGR_EMPTY, r);
+      if (cur == DGR_EMPTY) break;
+    }
+    if (dgr_rows_equal<NC>(keys + (int64_t)cur * NC, me)) break;
+    slot = (slot + 1) & mask;
+  }
+  *slot_out = slot;
+  return cur;
+}
+
+// table[slot] ends up holding the SMALLEST row among the inserted rows that share a key, whatever the order the threads
+// are served in.  A row that sees a smaller row of its key leaves without the atomic: a slot's value only ever falls.
+template <int NC>
+__device__ __forceinline__ void dgr_insert_first(int32_t *table, uint32_t mask, const int32_t *__restrict__ keys, int r) {
+  uint32_t slot;
+  const int prev = dgr_claim<NC>(table, mask, keys, r, &slot);
+  if (prev > r) atomicMin(&table[slot], r);
 }
 
 // Row index of `q` in (coords, table) or -1.

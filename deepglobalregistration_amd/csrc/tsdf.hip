@@ -7,8 +7,8 @@
 //   ts_depth_lut   d = raw / depth_scale for the 65536 raw values, -1 where the pixel is invalid (one division per VALUE)
 //   ts_multiplier  m[v][u] = sqrt((1 + ((u - cx)/fx)^2) + ((v - cy)/fy)^2), the ray length per unit depth, once per call
 //   ts_candidates  one thread per strided pixel: back-project, pose, the 2 x 2 x 2 blocks its truncation band touches
-//   ts_insert      the candidate enters the hash of its 3-int key; a slot keeps the SMALLEST candidate of a key
-//   ts_flag        flag = "I am the candidate the table holds for my key"; scan -> the block's place in the list
+//   unique rows    dgr_unique_rows over the 3-int keys, dropped candidates skipped: a slot of the hash keeps the SMALLEST
+//                  candidate of a key, flag = "I am that candidate", scan -> the block's place in the list
 //   ts_blocks      the flagged candidates write the block list                       -- host sync 1: nb
 //   ts_integrate   ONE WORKGROUP PER BLOCK (four per 16^3 block, a slab of z-layers each), voxel-stationary: a thread keeps
 //                  tsdf / weight of its voxels in registers over the whole frame loop and stores them once
@@ -19,12 +19,13 @@
 // floating-point atomics, and the only integer atomics (hash insertion, a statistics counter) are order-free.
 #include "dgr_internal.h"
 #include "hash.h"
+#include "scan.h"
+#include "tsdf_common.h"
 
 #include <cmath>
 #include <cstring>
 
 constexpr int TS_THREADS = 256;
-constexpr int32_t TS_DROPPED = -1, TS_PENDING = -2;
 constexpr double TS_BLOCK_LIMIT = (double)DGR_TSDF_BLOCK_LIMIT;
 
 struct TsCam {
@@ -103,46 +104,8 @@ __global__ void __launch_bounds__(TS_THREADS)
       dup |= up && ihi[a] == ilo[a];
       same &= k == (up ? phi[a] : plo[a]);
     }
-    row_first[row] = (valid && !dup && !same) ? TS_PENDING : TS_DROPPED;
+    row_first[row] = (valid && !dup && !same) ? DGR_ROW_PENDING : DGR_ROW_DROPPED;
   }
-}
-
-// voxelmean.hip's vm_insert / vm_flag (themselves coordmap.hip's unique_insert<3> / unique_flag with a skip of dropped
-// rows), copied once more so that no existing kernel source changes; the one difference: a row that already sees a smaller
-// row of its key in the slot leaves without the atomicMin (the slot's value only ever falls), which is nearly every row
-// here -- millions of candidates share a few thousand blocks.
-__global__ void __launch_bounds__(TS_THREADS)
-    ts_insert(const int32_t *__restrict__ keys, const int32_t *__restrict__ row_first, int64_t n, int32_t *table, uint32_t mask) {
-  const int64_t r = (int64_t)blockIdx.x * TS_THREADS + threadIdx.x;
-  if (r >= n || row_first[r] == TS_DROPPED) return;
-  const int32_t me[3] = {keys[r * 3], keys[r * 3 + 1], keys[r * 3 + 2]};
-  uint32_t slot = dgr_hash_row<3>(me) & mask;
-  while (true) {
-    int cur = __hip_atomic_load(&table[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == DGR_EMPTY) {
-      const int old = atomicCAS(&table[slot], DGR_EMPTY, (int)r);
-      if (old == DGR_EMPTY) return;
-      cur = old;
-    }
-    if (dgr_rows_equal<3>(keys + (int64_t)cur * 3, me)) {
-      if (cur > (int)r) atomicMin(&table[slot], (int)r);
-      return;
-    }
-    slot = (slot + 1) & mask;
-  }
-}
-
-__global__ void __launch_bounds__(TS_THREADS)
-    ts_flag(const int32_t *__restrict__ keys, int64_t n, const int32_t *__restrict__ table, uint32_t mask,
-            const int32_t *__restrict__ row_first, int32_t *__restrict__ flag) {
-  const int64_t r = (int64_t)blockIdx.x * TS_THREADS + threadIdx.x;
-  if (r >= n) return;
-  int f = 0;
-  if (row_first[r] != TS_DROPPED) {
-    const int32_t me[3] = {keys[r * 3], keys[r * 3 + 1], keys[r * 3 + 2]};
-    f = dgr_lookup<3>(table, mask, keys, me) == (int32_t)r;
-  }
-  flag[r] = f;
 }
 
 __global__ void __launch_bounds__(TS_THREADS)
@@ -167,17 +130,14 @@ __global__ void __launch_bounds__(TS_THREADS)
 // side of the four planes through the camera that bound [0, W) x [0, H) in (uf, vf).  A frame is skipped only if the ball
 // lies outside one of these half-spaces by a margin of 1 % of the radius + 1e-6 + 1e-9 |centre|, orders of magnitude above
 // the rounding of either side; the bitwise comparison with the uncalled statement is the proof that nothing is lost.
-// workgroups per block: a 16^3 block is four slabs of four z-layers (4 voxels per thread instead of 16: a fragment has
-// a few hundred such blocks, too few workgroups of 16 serial voxels per thread to fill 256 CUs evenly)
-template <int B> struct TsSplit { static constexpr int value = B == 16 ? 4 : 1; };
-
+// workgroups per block: TsdfSplit (tsdf_common.h)
 template <int B>
 __global__ void __launch_bounds__(TS_THREADS)
     ts_integrate(const int32_t *__restrict__ bkeys, const uint16_t *__restrict__ depth, const double *__restrict__ dlut,
                  const double *__restrict__ mtab, const double *__restrict__ ext, TsCam cam, float *__restrict__ tsdf_out,
                  int32_t *__restrict__ weight_out, unsigned long long *kept) {
 #pragma clang fp contract(off)
-  constexpr int SPLIT = TsSplit<B>::value, PART = B * B * B / SPLIT;
+  constexpr int SPLIT = TsdfSplit<B>::value, PART = B * B * B / SPLIT;
   constexpr int V = B * B * B, VPT = PART / TS_THREADS, ZSTEP = TS_THREADS / (B * B);
   __shared__ unsigned char keep[TS_THREADS];
   const int b = blockIdx.x / SPLIT, part = blockIdx.x % SPLIT, t = threadIdx.x;
@@ -269,10 +229,10 @@ __global__ void __launch_bounds__(TS_THREADS)
                double voxel, int min_weight, int32_t *__restrict__ counts, const int32_t *__restrict__ base, int64_t max_points,
                double *__restrict__ xyz) {
 #pragma clang fp contract(off)
-  constexpr int SPLIT = TsSplit<B>::value, PART = B * B * B / SPLIT;
+  constexpr int SPLIT = TsdfSplit<B>::value, PART = B * B * B / SPLIT;
   constexpr int V = B * B * B, VPT = PART / TS_THREADS;
   __shared__ int32_t nbr[3];
-  __shared__ int32_t scan[TS_THREADS];
+  __shared__ int32_t lds[TS_THREADS / 64];
   const int b = blockIdx.x / SPLIT, part = blockIdx.x % SPLIT, t = threadIdx.x;
   const int32_t bc[3] = {bkeys[(int64_t)b * 3], bkeys[(int64_t)b * 3 + 1], bkeys[(int64_t)b * 3 + 2]};
   if (t < 3) {
@@ -297,47 +257,37 @@ __global__ void __launch_bounds__(TS_THREADS)
       f1 = tsdf[o];
       w1 = weight[o];
     }
-    return w1 >= min_weight && f1 >= -0.98f && f1 < 0.98f && ((f0 < 0.f) != (f1 < 0.f));
+    return tsdf_usable(f1, w1, min_weight) && ((f0 < 0.f) != (f1 < 0.f));
   };
   int mine = 0;
   for (int k = 0; k < VPT; ++k) {
     const int l = part * PART + t * VPT + k;
     const float f0 = T0[l];
-    if (!(W0[l] >= min_weight && f0 >= -0.98f && f0 < 0.98f)) continue;
+    if (!tsdf_usable(f0, W0[l], min_weight)) continue;
     const int lc[3] = {l % B, (l / B) % B, l / (B * B)};
     for (int a = 0; a < 3; ++a) {
       float f1;
       mine += crossing(l, lc, a, f0, f1);
     }
   }
-  // inclusive scan of the 256 counts
-  scan[t] = mine;
-  __syncthreads();
-  for (int off = 1; off < TS_THREADS; off <<= 1) {
-    const int add = t >= off ? scan[t - off] : 0;
-    __syncthreads();
-    scan[t] += add;
-    __syncthreads();
-  }
+  int32_t total;
+  const int32_t before = dgr_block_exclusive<int32_t, TS_THREADS>(mine, lds, &total);
   if (!WRITE) {
-    if (t == TS_THREADS - 1) counts[blockIdx.x] = scan[t];
+    if (t == 0) counts[blockIdx.x] = total;
     return;
   }
-  int64_t at = (int64_t)base[blockIdx.x] + scan[t] - mine;
+  int64_t at = (int64_t)base[blockIdx.x] + before;
   for (int k = 0; k < VPT; ++k) {
     const int l = part * PART + t * VPT + k;
     const float f0 = T0[l];
-    if (!(W0[l] >= min_weight && f0 >= -0.98f && f0 < 0.98f)) continue;
+    if (!tsdf_usable(f0, W0[l], min_weight)) continue;
     const int lc[3] = {l % B, (l / B) % B, l / (B * B)};
     for (int a = 0; a < 3; ++a) {
       float f1;
       if (!crossing(l, lc, a, f0, f1)) continue;
       if (at < max_points) {   // (always: the host checked P <= max_points before this launch)
         double p[3];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) p[e] = ((double)(bc[e] * B + lc[e]) + 0.5) * voxel;
-        const double r0 = fabs((double)f0), r1 = fabs((double)f1);
-        p[a] = p[a] + voxel * (r0 / (r0 + r1));
+        tsdf_crossing_point<B>(bc, lc, a, f0, f1, voxel, p);
 #pragma unroll
         for (int e = 0; e < 3; ++e) xyz[at * 3 + e] = p[e];
       }
@@ -351,8 +301,8 @@ static int ts_run_blocks(const int32_t *bkeys, int64_t nb, const uint16_t *depth
                          const double *ext, const TsCam &cam, float *tsdf, int32_t *weight, unsigned long long *kept,
                          const int32_t *table, uint32_t mask, const int32_t *keys, const int32_t *rank, int min_weight,
                          int32_t *counts, hipStream_t stream) {
-  ts_integrate<B><<<(unsigned)(nb * TsSplit<B>::value), TS_THREADS, 0, stream>>>(bkeys, depth, dlut, mtab, ext, cam, tsdf, weight, kept);
-  ts_extract<B, 0><<<(unsigned)(nb * TsSplit<B>::value), TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight,
+  ts_integrate<B><<<(unsigned)(nb * TsdfSplit<B>::value), TS_THREADS, 0, stream>>>(bkeys, depth, dlut, mtab, ext, cam, tsdf, weight, kept);
+  ts_extract<B, 0><<<(unsigned)(nb * TsdfSplit<B>::value), TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight,
                                                             counts, nullptr, 0, nullptr);
   DGR_LAUNCH_CHECK();
   return DGR_OK;
@@ -411,9 +361,7 @@ extern "C" int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframe
     memcpy(pin + 64 + (size_t)f * 96, pose + (size_t)f * 16, 96);
     memcpy(pin + 64 + mat_bytes + (size_t)f * 96, extrinsic + (size_t)f * 16, 96);
   }
-  uint64_t cap64 = 64;
-  while (cap64 < 2 * (uint64_t)n && cap64 < (1ull << 31)) cap64 <<= 1;   // (as dgr_voxel_mean: n < 2^31 <= slots)
-  const uint32_t mask = (uint32_t)(cap64 - 1);
+  uint32_t mask;
   double *mats, *dlut, *mtab;
   int32_t *keys, *row_first, *flag, *rank, *table, *counters;   // counters[0] = blocks, [1] = points, [2..3] = kept (u64)
   DGR_ALLOC(mats, A, double, (size_t)nframes * 24);
@@ -423,20 +371,16 @@ extern "C" int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframe
   DGR_ALLOC(row_first, A, int32_t, n);
   DGR_ALLOC(flag, A, int32_t, n);
   DGR_ALLOC(rank, A, int32_t, n);
-  DGR_ALLOC(table, A, int32_t, cap64);
   DGR_ALLOC(counters, A, int32_t, 4);
   const double *pose_dev = mats, *ext_dev = mats + (size_t)nframes * 12;
   DGR_HIP_CHECK(hipMemcpyAsync(mats, pin + 64, 2 * mat_bytes, hipMemcpyHostToDevice, stream));
-  DGR_HIP_CHECK(hipMemsetAsync(table, 0xff, (size_t)cap64 * sizeof(int32_t), stream));
   DGR_HIP_CHECK(hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), stream));
   ts_depth_lut<<<65536 / TS_THREADS, TS_THREADS, 0, stream>>>(depth_scale, depth_trunc, dlut);
   ts_multiplier<<<(unsigned)dgr_ceil_div((int64_t)height * width, TS_THREADS), TS_THREADS, 0, stream>>>(cam, mtab);
   const unsigned grid = (unsigned)dgr_ceil_div(n, TS_THREADS);
   ts_candidates<<<(unsigned)dgr_ceil_div(ns, TS_THREADS), TS_THREADS, 0, stream>>>(depth, dlut, pose_dev, cam, ns, keys, row_first);
-  ts_insert<<<grid, TS_THREADS, 0, stream>>>(keys, row_first, n, table, mask);
-  ts_flag<<<grid, TS_THREADS, 0, stream>>>(keys, n, table, mask, row_first, flag);
   DGR_LAUNCH_CHECK();
-  DGR_CHECK(dgr_exclusive_scan_i32(A, flag, rank, n, counters, stream));
+  DGR_CHECK(dgr_unique_rows(A, keys, n, 3, row_first, nullptr, flag, rank, counters, &table, &mask, stream));
   DGR_HIP_CHECK(hipMemcpyAsync(pin, counters, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   DGR_CHECK(dgr_ctx_wait(ctx, stream));   // synchronisation 1: the number of blocks sizes the volume
   int32_t nb32;
@@ -459,7 +403,7 @@ extern "C" int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframe
     DGR_ALLOC(tsdf, A, float, nb * V);
     DGR_ALLOC(weight, A, int32_t, nb * V);
   }
-  const int64_t ngroups = nb * (block == 16 ? TsSplit<16>::value : TsSplit<8>::value);   // workgroups of the per-block kernels
+  const int64_t ngroups = nb * (block == 16 ? TsdfSplit<16>::value : TsdfSplit<8>::value);   // workgroups of the per-block kernels
   DGR_ALLOC(counts, A, int32_t, ngroups);
   DGR_ALLOC(base, A, int32_t, ngroups);
   ts_blocks<<<grid, TS_THREADS, 0, stream>>>(keys, flag, rank, n, nb, bkeys);
@@ -488,10 +432,10 @@ extern "C" int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframe
   }
   if (P == 0) return DGR_OK;
   if (block == 8)
-    ts_extract<8, 1><<<(unsigned)(nb * TsSplit<8>::value), TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight,
+    ts_extract<8, 1><<<(unsigned)(nb * TsdfSplit<8>::value), TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight,
                                                               nullptr, base, max_points, xyz_out);
   else
-    ts_extract<16, 1><<<(unsigned)(nb * TsSplit<16>::value), TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight,
+    ts_extract<16, 1><<<(unsigned)(nb * TsdfSplit<16>::value), TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight,
                                                                nullptr, base, max_points, xyz_out);
   DGR_LAUNCH_CHECK();
   return DGR_OK;

@@ -18,6 +18,8 @@
 // atomics are the hash insertion and the flag word, both order-free.  No floating-point atomics.
 #include "dgr_internal.h"
 #include "hash.h"
+#include "scan.h"
+#include "tsdf_common.h"
 
 #define DGR_MC_TABLE_QUALIFIER static __device__ const
 #include "mc_table.h"
@@ -28,8 +30,6 @@
 constexpr int MS_THREADS = 256;
 constexpr int MS_FLAG_RANGE = 1, MS_FLAG_TWICE = 2;
 constexpr unsigned char MS_POS = 0, MS_NEG = 1, MS_UNUSABLE = 2;
-
-template <int B> struct MsSplit { static constexpr int value = B == 16 ? 4 : 1; };
 
 __global__ void __launch_bounds__(MS_THREADS)
     ms_insert(const int32_t *__restrict__ blocks, int64_t nb, int32_t *table, uint32_t mask, int32_t *flag) {
@@ -43,20 +43,8 @@ __global__ void __launch_bounds__(MS_THREADS)
     atomicOr(flag, MS_FLAG_RANGE);
     return;
   }
-  uint32_t slot = dgr_hash_row<3>(me) & mask;
-  while (true) {   // (ends: the table has at least twice as many slots as there are rows)
-    int cur = __hip_atomic_load(&table[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == DGR_EMPTY) {
-      const int old = atomicCAS(&table[slot], DGR_EMPTY, (int)r);
-      if (old == DGR_EMPTY) return;
-      cur = old;
-    }
-    if (dgr_rows_equal<3>(blocks + (int64_t)cur * 3, me)) {
-      atomicOr(flag, MS_FLAG_TWICE);
-      return;
-    }
-    slot = (slot + 1) & mask;
-  }
+  uint32_t slot;
+  if (dgr_claim<3>(table, mask, blocks, (int)r, &slot) != DGR_EMPTY) atomicOr(flag, MS_FLAG_TWICE);
 }
 
 // The volume as one workgroup sees it: local coordinates in [-1, B + 1] per axis, resolved through the 27 blocks around
@@ -90,11 +78,11 @@ __global__ void __launch_bounds__(MS_THREADS)
             int32_t *__restrict__ edge_vertex, int64_t max_vertices, int64_t max_triangles, double *__restrict__ xyz,
             double *__restrict__ normal, int32_t *__restrict__ tri) {
 #pragma clang fp contract(off)
-  constexpr int SPLIT = MsSplit<B>::value, V = B * B * B, PART = V / SPLIT, VPT = PART / MS_THREADS;
+  constexpr int SPLIT = TsdfSplit<B>::value, V = B * B * B, PART = V / SPLIT, VPT = PART / MS_THREADS;
   constexpr int LAYERS = B / SPLIT, TX = B + 1, TZ = LAYERS + 1, TILE = TX * TX * TZ;
   __shared__ int32_t nbr[27];
   __shared__ unsigned char state[TILE];
-  __shared__ int32_t scan[MS_THREADS];
+  __shared__ int32_t lds[MS_THREADS / 64];
   const int b = blockIdx.x / SPLIT, part = blockIdx.x % SPLIT, t = threadIdx.x, z0 = part * LAYERS;
   const int32_t bc[3] = {blocks[(int64_t)b * 3], blocks[(int64_t)b * 3 + 1], blocks[(int64_t)b * 3 + 2]};
   if (t < 27) {
@@ -109,7 +97,7 @@ __global__ void __launch_bounds__(MS_THREADS)
     unsigned char s = MS_UNUSABLE;
     if (o >= 0) {
       const float f = tsdf[o];
-      if (weight[o] >= min_weight && f >= -0.98f && f < 0.98f) s = f < 0.f ? MS_NEG : MS_POS;
+      if (tsdf_usable(f, weight[o], min_weight)) s = f < 0.f ? MS_NEG : MS_POS;
     }
     state[i] = s;
   }
@@ -142,24 +130,16 @@ __global__ void __launch_bounds__(MS_THREADS)
       nt += cfg < 0 ? 0 : dgr_mc_count[cfg];
     }
   }
-  // inclusive scan of both counts at once: at most 3 VPT 256 = 3072 vertices and 5 VPT 256 = 5120 triangles a workgroup
-  const int mine = nv | nt << 16;
-  scan[t] = mine;
-  __syncthreads();
-  for (int off = 1; off < MS_THREADS; off <<= 1) {
-    const int add = t >= off ? scan[t - off] : 0;
-    __syncthreads();
-    scan[t] += add;
-    __syncthreads();
-  }
+  // both counts in one scan: at most 3 VPT 256 = 3072 vertices and 5 VPT 256 = 5120 triangles a workgroup
+  int32_t total;
+  const int32_t before = dgr_block_exclusive<int32_t, MS_THREADS>(nv | nt << 16, lds, &total);
   if (MODE == 0) {
-    if (t == MS_THREADS - 1) {
-      vcounts[blockIdx.x] = scan[t] & 0xffff;
-      tcounts[blockIdx.x] = scan[t] >> 16;
+    if (t == 0) {
+      vcounts[blockIdx.x] = total & 0xffff;
+      tcounts[blockIdx.x] = total >> 16;
     }
     return;
   }
-  const int before = scan[t] - mine;
   if (MODE == 1) {
     int64_t at = (int64_t)vbase[blockIdx.x] + (before & 0xffff);
     for (int k = 0; k < VPT; ++k) {
@@ -174,11 +154,7 @@ __global__ void __launch_bounds__(MS_THREADS)
           hc[a] += 1;
           const float f0 = tsdf[(int64_t)b * V + l], f1 = tsdf[view.at(hc[0], hc[1], hc[2])];
           double p[3];
-#pragma unroll
-          for (int e = 0; e < 3; ++e) p[e] = ((double)(bc[e] * B + lc[e]) + 0.5) * voxel;
-          const double r0 = fabs((double)f0), r1 = fabs((double)f1);
-          const double r = r0 / (r0 + r1);
-          p[a] = p[a] + voxel * r;
+          const double r = tsdf_crossing_point<B>(bc, lc, a, f0, f1, voxel, p);
 #pragma unroll
           for (int e = 0; e < 3; ++e) xyz[at * 3 + e] = p[e];
           if (normal) {
@@ -230,7 +206,7 @@ static void ms_launch(int mode, int64_t nb, const int32_t *blocks, const float *
                       uint32_t mask, double voxel, int min_weight, int32_t *vcounts, int32_t *tcounts, const int32_t *vbase,
                       const int32_t *tbase, int32_t *edge_vertex, int64_t max_vertices, int64_t max_triangles, double *xyz,
                       double *normal, int32_t *tri, hipStream_t stream) {
-  const unsigned grid = (unsigned)(nb * MsSplit<B>::value);
+  const unsigned grid = (unsigned)(nb * TsdfSplit<B>::value);
 #define MS_ARGS blocks, tsdf, weight, table, mask, voxel, min_weight, vcounts, tcounts, vbase, tbase, edge_vertex, max_vertices, \
                 max_triangles, xyz, normal, tri
   if (mode == 0) ms_pass<B, 0><<<grid, MS_THREADS, 0, stream>>>(MS_ARGS);
@@ -266,19 +242,16 @@ extern "C" int dgr_tsdf_mesh(dgr_ctx *ctx, const int32_t *blocks, int64_t n_bloc
   DgrArena &A = ctx->arena;
   unsigned char *pin;
   DGR_CHECK(dgr_ctx_pinned(ctx, 64, &pin));
-  uint64_t cap = 64;
-  while (cap < 2 * (uint64_t)nb) cap <<= 1;
-  const uint32_t mask = (uint32_t)(cap - 1);
-  const int64_t ngroups = nb * (block == 16 ? MsSplit<16>::value : MsSplit<8>::value);
+  uint32_t mask;
+  const int64_t ngroups = nb * (block == 16 ? TsdfSplit<16>::value : TsdfSplit<8>::value);
   int32_t *table, *counters, *vcounts, *tcounts, *vbase, *tbase, *edge_vertex;   // counters: vertices, triangles, flag
-  DGR_ALLOC(table, A, int32_t, cap);
+  DGR_CHECK(dgr_table_make(A, nb, &table, &mask, stream));
   DGR_ALLOC(counters, A, int32_t, 4);
   DGR_ALLOC(vcounts, A, int32_t, ngroups);
   DGR_ALLOC(tcounts, A, int32_t, ngroups);
   DGR_ALLOC(vbase, A, int32_t, ngroups);
   DGR_ALLOC(tbase, A, int32_t, ngroups);
   DGR_ALLOC(edge_vertex, A, int32_t, nb * V * 3);
-  DGR_HIP_CHECK(hipMemsetAsync(table, 0xff, (size_t)cap * sizeof(int32_t), stream));
   DGR_HIP_CHECK(hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), stream));
   ms_insert<<<(unsigned)dgr_ceil_div(nb, MS_THREADS), MS_THREADS, 0, stream>>>(blocks, nb, table, mask, counters + 2);
   auto launch = [&](int mode) {

@@ -5,9 +5,9 @@
 //
 // Passes (one thread per selected row unless noted; rows are numbered in ascending row of `xyz`):
 //   vm_quantise    pose, u = (p - origin) / voxel, c = floor(u), k = floor((u - c) 2^40); dropped rows are counted
-//   vm_insert      the row enters the hash of its 3-int key (table sized 2x rows, a slot keeps the SMALLEST row of a key)
-//   vm_flag        the row's voxel = the row the table holds for its key; flag = "I am that row"
-//   scan           exclusive scan of the flags: rank of a voxel = first-occurrence order (dgr_exclusive_scan_i32)
+//   unique rows    dgr_unique_rows over the 3-int keys, dropped rows skipped: the row's voxel = the smallest row of its key
+//                  (kept in row_first), flag = "I am that row", rank of a voxel = first-occurrence order; a call of its own
+//                  behind vm_quantise, so that every key it compares against was written by a finished kernel
 //   vm_clear       zeroes count and sums of the V voxels (V is known on the device only)
 //   vm_accumulate  no-return integer atomics: count += 1 (int32), sums += k (3 x uint64); first rows write first / coords
 //   vm_finalise    one thread per voxel: mean = origin + (c + S / (n 2^40)) voxel
@@ -15,7 +15,6 @@
 // Determinism: every per-row value is a function of the row alone and integer addition is associative and commutative,
 // so the order in which the atomics are served does not reach the result -- no floating-point atomics anywhere.
 #include "dgr_internal.h"
-#include "hash.h"
 
 #include <algorithm>
 #include <cmath>
@@ -24,7 +23,6 @@
 
 constexpr int VM_THREADS = 256;
 constexpr double VM_FRAC_SCALE = (double)(1ull << DGR_VM_FRAC_BITS);
-constexpr int32_t VM_DROPPED = -1, VM_PENDING = -2;
 
 // one selected fragment, in ascending fragment order
 struct VmSeg {
@@ -45,32 +43,6 @@ __device__ __forceinline__ int vm_segment_of(const int64_t *__restrict__ base, i
     if (base[mid] <= r) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-// table[slot] ends up holding the smallest row among the valid rows that share a key.  This is coordmap.hip's
-// unique_insert<3> with one more test, the skip of dropped rows, and vm_flag below is its unique_flag with the same skip
-// and the row's voxel kept: COPIES, on purpose -- the map builders' kernels are on the timed registration path and this
-// file changes none of them; whoever changes the probe loop there changes it here.  A kernel of its own behind
-// vm_quantise, so that every key it compares against was written by a finished kernel.
-__global__ void __launch_bounds__(VM_THREADS)
-    vm_insert(const int32_t *__restrict__ keys, const int32_t *__restrict__ row_first, int64_t n, int32_t *table, uint32_t mask) {
-  const int64_t r = (int64_t)blockIdx.x * VM_THREADS + threadIdx.x;
-  if (r >= n || row_first[r] == VM_DROPPED) return;
-  const int32_t me[3] = {keys[r * 3], keys[r * 3 + 1], keys[r * 3 + 2]};
-  uint32_t slot = dgr_hash_row<3>(me) & mask;
-  while (true) {
-    int cur = __hip_atomic_load(&table[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == DGR_EMPTY) {
-      const int old = atomicCAS(&table[slot], DGR_EMPTY, (int)r);
-      if (old == DGR_EMPTY) return;
-      cur = old;
-    }
-    if (dgr_rows_equal<3>(keys + (int64_t)cur * 3, me)) {
-      atomicMin(&table[slot], (int)r);
-      return;
-    }
-    slot = (slot + 1) & mask;
-  }
 }
 
 template <typename T>
@@ -106,25 +78,10 @@ __global__ void __launch_bounds__(VM_THREADS)
       keys[r * 3 + d] = c[d];
       frac[r * 3 + d] = k[d];
     }
-    row_first[r] = drop ? VM_DROPPED : VM_PENDING;
+    row_first[r] = drop ? DGR_ROW_DROPPED : DGR_ROW_PENDING;
   }
   const unsigned long long b = __ballot(drop);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(dropped, __popcll(b));
-}
-
-__global__ void __launch_bounds__(VM_THREADS)
-    vm_flag(const int32_t *__restrict__ keys, int64_t n, const int32_t *__restrict__ table, uint32_t mask,
-            int32_t *__restrict__ row_first, int32_t *__restrict__ flag) {
-  const int64_t r = (int64_t)blockIdx.x * VM_THREADS + threadIdx.x;
-  if (r >= n) return;
-  int f = 0;
-  if (row_first[r] != VM_DROPPED) {
-    const int32_t me[3] = {keys[r * 3], keys[r * 3 + 1], keys[r * 3 + 2]};
-    const int v = dgr_lookup<3>(table, mask, keys, me);
-    row_first[r] = v;
-    f = v == (int32_t)r;
-  }
-  flag[r] = f;
 }
 
 __global__ void __launch_bounds__(VM_THREADS)
@@ -228,13 +185,9 @@ extern "C" int dgr_voxel_mean(dgr_ctx *ctx, const void *xyz, int is_f64, const i
   DGR_CHECK(dgr_ctx_pinned(ctx, 64 + seg_bytes + base_bytes, &pin));
   memcpy(pin + 64, hsegs.data(), seg_bytes);
   memcpy(pin + 64 + seg_bytes, hbase.data(), base_bytes);
-  // open addressing at a load of at most 1/2 (a table of 2^31 slots, the most a 32-bit mask addresses, above 2^30 rows)
-  uint64_t cap64 = 64;
-  while (cap64 < 2 * (uint64_t)n && cap64 < (1ull << 31)) cap64 <<= 1;
-  const uint32_t mask = (uint32_t)(cap64 - 1);
   VmSeg *segs;
   int64_t *seg_base;
-  int32_t *keys, *row_first, *flag, *rank, *table, *counters;   // counters[0] = voxels, [1] = dropped rows
+  int32_t *keys, *row_first, *flag, *rank, *counters;   // counters[0] = voxels, [1] = dropped rows
   unsigned long long *frac, *sums = reinterpret_cast<unsigned long long *>(fsum_out);
   DGR_ALLOC(segs, A, VmSeg, nsel);
   DGR_ALLOC(seg_base, A, int64_t, nsel);
@@ -243,12 +196,10 @@ extern "C" int dgr_voxel_mean(dgr_ctx *ctx, const void *xyz, int is_f64, const i
   DGR_ALLOC(row_first, A, int32_t, n);
   DGR_ALLOC(flag, A, int32_t, n);
   DGR_ALLOC(rank, A, int32_t, n);
-  DGR_ALLOC(table, A, int32_t, cap64);
   DGR_ALLOC(counters, A, int32_t, 2);
   if (!sums) DGR_ALLOC(sums, A, unsigned long long, n * 3);
   DGR_HIP_CHECK(hipMemcpyAsync(segs, pin + 64, seg_bytes, hipMemcpyHostToDevice, stream));
   DGR_HIP_CHECK(hipMemcpyAsync(seg_base, pin + 64 + seg_bytes, base_bytes, hipMemcpyHostToDevice, stream));
-  DGR_HIP_CHECK(hipMemsetAsync(table, 0xff, (size_t)cap64 * sizeof(int32_t), stream));
   DGR_HIP_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(int32_t), stream));
   VmLattice L;
   for (int d = 0; d < 3; ++d) L.origin[d] = origin[d];
@@ -260,10 +211,10 @@ extern "C" int dgr_voxel_mean(dgr_ctx *ctx, const void *xyz, int is_f64, const i
   else
     vm_quantise<float><<<grid, VM_THREADS, 0, stream>>>((const float *)xyz, segs, seg_base, nsel, T != nullptr, L, n, keys, frac,
                                                         row_first, counters + 1);
-  vm_insert<<<grid, VM_THREADS, 0, stream>>>(keys, row_first, n, table, mask);
-  vm_flag<<<grid, VM_THREADS, 0, stream>>>(keys, n, table, mask, row_first, flag);
   DGR_LAUNCH_CHECK();
-  DGR_CHECK(dgr_exclusive_scan_i32(A, flag, rank, n, counters, stream));
+  int32_t *table;   // (the key hash: not read again here)
+  uint32_t mask;
+  DGR_CHECK(dgr_unique_rows(A, keys, n, 3, row_first, row_first, flag, rank, counters, &table, &mask, stream));
   vm_clear<<<grid, VM_THREADS, 0, stream>>>(counters, count_out, sums);
   vm_accumulate<<<grid, VM_THREADS, 0, stream>>>(keys, frac, row_first, rank, segs, seg_base, nsel, n, first_out, coords_out,
                                                  count_out, sums);

@@ -138,6 +138,30 @@ def test_far_apart_clusters_take_the_cell_doubling_path():
     np.testing.assert_array_equal(_gpu_pairs(x0, x1, np.eye(4), 0.01), want)
 
 
+def test_262145_source_rows_reach_the_carry_of_the_block_scan():
+    """The offsets of the source rows are scanned in blocks of 1024 rows and the block sums by ONE workgroup, 256 at a
+    time with a carry: 262 145 rows are 257 blocks, the first size with a second round.  Rows 0 .. 262 144 of a 64 x 64 x 65
+    integer lattice as two batch entries; entry p's targets are its own rows with row % 3 != p, moved by 1/4 along x and
+    shuffled -- at r = 1/2 every source row has its moved self (d = 1/4) or nothing (the next point is 3/4 away), all
+    exact under the identity pose, so pairs and pair_off follow from the lattice."""
+    from deepglobalregistration_amd import ops
+    g = np.arange(65, dtype=np.float32)
+    N, cut = 262145, 131072
+    x0 = np.stack(np.meshgrid(g[:64], g[:64], g, indexing='ij'), -1).reshape(-1, 3)[:N]
+    rng = np.random.default_rng(21)
+    x1s, want, off1 = [], [], [0]
+    for p, (lo, hi) in enumerate([(0, cut), (cut, N)]):
+        rows = lo + np.nonzero(np.arange(lo, hi) % 3 != p)[0]
+        perm = rng.permutation(len(rows))                            # target j is source row rows[perm[j]]
+        x1s.append(x0[rows[perm]] + np.array([0.25, 0, 0], np.float32))
+        want.append(np.stack((rows - lo, np.argsort(perm)), 1))
+        off1.append(off1[-1] + len(rows))
+    T = np.tile(np.eye(4), (2, 1, 1))
+    pairs, pair_off = ops.radius_pairs_batch(x0, [0, cut, N], np.concatenate(x1s), off1, T, 0.5)
+    assert pair_off.tolist() == [0, len(want[0]), len(want[0]) + len(want[1])] and len(want[1]) > 80000
+    np.testing.assert_array_equal(pairs.cpu().numpy(), np.concatenate(want))
+
+
 def test_non_finite_rows_take_no_part():
     rng = np.random.default_rng(5)
     x1 = rng.uniform(0, 1, (300, 3)).astype(np.float32)

@@ -249,6 +249,16 @@ def test_argument_errors_are_reported_not_launched():
     assert rc == _lib.DGR_EINVAL and b'twice' in lib.dgr_last_error()
     with pytest.raises(ValueError, match='twice'):
         ops.tsdf_mesh(twice, tsdf, weight, 1.0, block=8)
+    # ... also when the two copies lie in different workgroups of the insertion (256 list entries each): 320 unobserved
+    # blocks along x are an empty mesh, the same list with entry 300 = entry 0 is an error
+    row = torch.zeros((320, 3), dtype=torch.int32, device=dev)
+    row[:, 0] = torch.arange(320, dtype=torch.int32, device=dev)
+    empty = dict(good, blocks=row, tsdf=torch.zeros((320, 8, 8, 8), dtype=torch.float32, device=dev),
+                 weight=torch.zeros((320, 8, 8, 8), dtype=torch.int32, device=dev))
+    assert _raw_call(lib, ctx, **empty) == (_lib.DGR_OK, 0, 0)
+    row[300] = row[0]
+    rc, _, _ = _raw_call(lib, ctx, **empty)
+    assert rc == _lib.DGR_EINVAL and b'twice' in lib.dgr_last_error()
     # the wrapper's own checks: nothing reaches the library
     for kw, args3 in ((dict(block=4), None), (dict(min_weight=0), None), (dict(voxel_length=0.0), None),
                       (dict(voxel_length=float('nan')), None), (dict(block=16), None), ({}, (blocks.long(), tsdf, weight)),

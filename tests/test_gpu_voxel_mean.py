@@ -153,9 +153,26 @@ def test_lattice_range_and_dropped_rows():
         np.testing.assert_array_equal(dirty[k], clean[k])
 
 
+def test_dropped_rows_share_the_key_of_a_valid_voxel():
+    """A dropped row is stored with the key (0, 0, 0).  Rows 0 .. 299 are NaN; row 300 and a few later rows, in other
+    workgroups of the insert and flag kernels, are real points of voxel (0, 0, 0): the voxel's first row is 300 and its
+    count leaves the NaN rows out -- unless the shared unique kernels lose the skip of dropped rows."""
+    rng = np.random.default_rng(12)
+    N, inside = 1500, [300, 301, 555, 700, 1023, 1024, 1499]
+    x = rng.uniform(0.3, 0.9, (N, 3))                                # voxels (1..3, 1..3, 1..3) of 25 cm
+    x[:300] = np.nan
+    x[inside] = rng.uniform(0.01, 0.24, (len(inside), 3))
+    for dtype in (np.float64, np.float32):
+        g = _check(x.astype(dtype), 0.25, what=f'NaN rows before voxel 0, {np.dtype(dtype).name}')
+        assert g['dropped'] == 300 and g['coords'][0].tolist() == [0, 0, 0]
+        assert g['first'][0] == 300 and g['count'][0] == len(inside) and g['count'].sum() == N - 300
+
+
 # ---- 4. shapes -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('N', [1, 63, 64, 65, 255, 256, 257, 1024, 1025, 2048])
+@pytest.mark.parametrize('N', [1, 63, 64, 65, 255, 256, 257, 1024, 1025, 2048, 4096, 4097, 16384, 16385])
 def test_row_counts_around_the_block_sizes(N):
+    """(4096 / 4097: the one-workgroup scan of the flags starts a second round with a carry; 16384 / 16385: the last size of
+    that scan and the first of the three-launch one.)"""
     rng = np.random.default_rng(N)
     x = rng.uniform(-0.4, 0.4, (N, 3)).astype(np.float32)           # ~4000 voxels of 5 cm: several points per voxel
     cut = N // 3
