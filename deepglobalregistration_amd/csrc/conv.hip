@@ -33,13 +33,6 @@
 #include "hash.h"
 #include "split.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct ConvKArgs {
   const float *in;
   float *out;          // identity maps: written directly (acc + shift); otherwise unused
@@ -549,21 +542,13 @@ __global__ void __launch_bounds__(256)
       // consumers' pending ReLU (the LPR lanes of a row are consecutive lanes of one wave), two f16 planes
       const int lo = out_relu ? 0 : (int)0x80000000;
       const i32x4 ab = __builtin_bit_cast(i32x4, acc);   // (bit_cast of a single vector ELEMENT reads element 0)
-      int xb[4];
-      uint32_t mx = 0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        xb[u] = max(ab[u], lo);   // pending ReLU as one integer max
-        mx = max(mx, (uint32_t)xb[u] & 0x7fffffffu);
-      }
-#pragma unroll
-      for (int d = LPR / 2; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+      const uint32_t mx = dgr_lane_max<LPR>(dgr_abs_max4(ab, lo));
       const float sx = dgr_row_scale_of(mx);
       f16x4 h, m;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         _Float16 hh, mm;
-        dgr_split2(__builtin_bit_cast(float, xb[u]), sx, hh, mm);
+        dgr_split2(__builtin_bit_cast(float, max(ab[u], lo)), sx, hh, mm);   // pending ReLU as one integer max
         h[u] = hh; m[u] = mm;
       }
       // lanes 2 j and 2 j + 1 hold channels 8 j .. 8 j + 3 and 8 j + 4 .. 8 j + 7: they swap one piece, so that the even
@@ -871,9 +856,7 @@ __global__ void __launch_bounds__(256)
     }
     if (lane < 32) out[o * out_ld + co] = acc;
     if (out_amax) {   // (both half-waves hold the same 32 channels)
-      uint32_t mx = __builtin_bit_cast(uint32_t, acc) & 0x7fffffffu;
-#pragma unroll
-      for (int d = 16; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+      const uint32_t mx = dgr_lane_max<32>(dgr_abs_bits(acc));
       if (lane == 0) atomicMax(out_amax + o, mx);
     }
   }
@@ -1108,9 +1091,7 @@ __global__ void __launch_bounds__(256)
     const int64_t o = o0 + vsel;
     if (o < n) out[o * out_ld + co] = acc;
     if (out_amax) {   // a voxel's 32 channels are the 32 lanes of a half-wave
-      uint32_t mx = o < n ? (__builtin_bit_cast(uint32_t, acc) & 0x7fffffffu) : 0u;
-#pragma unroll
-      for (int d = 16; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+      const uint32_t mx = dgr_lane_max<32>(o < n ? dgr_abs_bits(acc) : 0u);
       if (co == 0 && o < n) atomicMax(out_amax + o, mx);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1195,8 +1176,6 @@ __global__ void __launch_bounds__(256)
         }
       }
     };
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     cells_of(0);
     fill(0);
@@ -1224,14 +1203,12 @@ __global__ void __launch_bounds__(256)
         f32x4 v = acc[jb];
         if (shift) v += *reinterpret_cast<const f32x4 *>(shift + 16 * jb + 4 * (lane >> 4));
         *reinterpret_cast<f32x4 *>(out + o * out_ld + 16 * jb + 4 * (lane >> 4)) = v;
-        const i32x4 b = __builtin_bit_cast(i32x4, v);
-        mx = max(mx, max(max((uint32_t)b.x & 0x7fffffffu, (uint32_t)b.y & 0x7fffffffu), max((uint32_t)b.z & 0x7fffffffu, (uint32_t)b.w & 0x7fffffffu)));
+        mx = max(mx, dgr_abs_max4(__builtin_bit_cast(i32x4, v)));
       }
     }
     if (out_amax) {   // the row's largest |x| for its split-operand consumers (conv_os.hip / conv_dense.hip): a voxel's
                       // channels sit in the four lanes (lane & 15) + 16 q
-      mx = max(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
-      mx = max(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
+      mx = dgr_lane_max<4, 16>(mx);
       if (lane < 16 && o < n) atomicMax(out_amax + o, mx);
     }
   }

@@ -35,16 +35,10 @@
 // Weight layout: the split pieces of conv_os.hip, WB[piece][k][s][jb][lane] = 8 halves =
 // W_folded[k][32 s + 8 (lane >> 4) + e][16 jb + (lane & 15)], re-ordered per fragment group for the gather's channel
 // order: lane (col, lq) holds half (lq & 1) of the natural fragments of lanes (col, lq >> 1) and (col, (lq >> 1) + 2) (net.hip).
-#include "dgr_internal.h"
-#include "split.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // (native vector: HIP's uint4 struct copies as memcpy and stays in scratch)
+//
+// The gather, the operand build, the MFMA step and the row epilogue are the pieces of dense_tile.h, shared with the
+// parity-class transposed conv (conv_up.hip); here: the block order, the weight ring and the offset loop around them.
+#include "dense_tile.h"
 
 #ifndef DGR_DENSE_RG
 #define DGR_DENSE_RG 2      // 16-row groups per wave with 64 input or output channels ...
@@ -55,25 +49,16 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // (native vec
 #ifndef DGR_DENSE_WD
 #define DGR_DENSE_WD 8      // weight ring: at most this many steps in flight
 #endif
-struct ConvDenseArgs {
-  const float *in;
-  float *out;
-  const float *shift, *res;
-  const u32x4 *wb;         // split weights: two f16 pieces, each [27][CIN/32][COUT/16][64] x 16 bytes
-  int64_t piece_stride;    // 16-byte units per piece
-  const int32_t *nbr, *n_out_dev;
-  int64_t n_pad;
-  int in_ld, in_relu, out_ld, out_relu, res_ld, res_relu;
-  const uint32_t *row_amax;   // bits of every input row's largest |x| after the pending ReLU (from the row's producer)
-  uint32_t *out_amax, *out_amax2;   // (nullable) the same for the rows written here: atomicMax per row
-  float w_unscale;         // inverse of the layer's weight scale
-  uint32_t in_bytes;       // size of the input tensor (row capacity x row stride): bound of the buffer loads
+struct ConvDenseArgs : DenseTileArgs {
+  const float *res;
+  const int32_t *n_out_dev;
+  int res_ld, res_relu;
   // Rows as READY-MADE OPERANDS (round 6).  in_ds: the input tensor written by its producer as "dense split rows" -- per
   // row 4 CIN bytes = [h plane: CIN halves][m plane: CIN halves], the two f16 pieces of scale(row) * max(x, 0 if ReLU),
   // every 32-channel group in THIS kernel's gather order (16-byte chunk c = channels 32 s + 4 c .. + 3 and 32 s + 16 + 4 c
   // .. + 3): the offset loop then holds no conversion at all (it was 4/5 of the kernel's vector instructions, more issue
   // cycles than its MFMAs).  out_ds: the rows written here in that form for the next dense-tile layer (the middle tensor
-  // of a residual block: `out` may then be null).  Same dgr_row_scale_of / dgr_split2 arithmetic on the same values as the
+  // of a residual block: `out` may then be null).  The same dgr_row_scale_of / dgr_split2_x8 (split.h) on the same values as the
   // consumer-side split: bit-identical results (tests/test_gpu_dense_conv.py).
   const unsigned char *in_ds;
   unsigned char *out_ds;
@@ -146,55 +131,25 @@ __global__ void __launch_bounds__(64 * WAVES, 2) sparse_conv_dense_f16x2(ConvDen
   // gathered rows of the NEXT offset: requested here, consumed (split into pieces) at the top of the next iteration
   const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       PS ? (void *)const_cast<unsigned char *>(a.in_ds) : (void *)const_cast<float *>(a.in), 0, a.in_bytes, 0x00020000);
-  // the gathered rows of one offset (raw f32, requested DEPTH offsets ahead), their row scales and table entries
-  struct RowSet { f32x4 raw[RG][S][2]; uint32_t mx[RG]; int nv[RG]; };
-  // Request layout: lane L = 4 r + c reads 16 bytes of row r of the group so that every QUAD of lanes reads 64
-  // contiguous bytes of one row -- one request of the vector-memory path per quad.  (Requesting straight in MFMA
-  // operand layout, lane = 16 chunk + row, makes every lane of a quad touch a different row: four requests per quad,
-  // measured 64 cycles per instruction and the kernel bounded by nothing else.)  The operand layout is restored after
-  // the split by ds_bpermute (the LDS crossbar, no LDS memory).
-  auto gather = [&](int k, RowSet &g) {
-    // unconditional requests: no branches in the loop body, so that the requests stay where they are written
-    // (conv_os.hip, same reason)
-#pragma unroll
-    for (int rg = 0; rg < RG; ++rg) {
-      const int n = nbr_s[k][(wave * RG + rg) * 16 + (lane >> 2)];
-      const int ne = max(n, 0);
-      // buffer loads: a missing neighbour gets an offset past the tensor -- the bounds check returns zeros without a
-      // memory access, and the request stays branch-free
-      const uint32_t off = n >= 0 ? (uint32_t)n * (uint32_t)((PS ? CIN : a.in_ld) * 4) + 16u * (lane & 3) : a.in_bytes;
-      const uint32_t mv = a.row_amax[ne];
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        if constexpr (PS) {   // chunk (lane & 3) of the 32-channel group's h plane and of its m plane
-          g.raw[rg][s][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off + 64 * s, 0, 0));
-          g.raw[rg][s][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off + 2 * CIN + 64 * s, 0, 0));
-        } else {
-          g.raw[rg][s][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off + 128 * s, 0, 0));
-          g.raw[rg][s][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off + 128 * s + 64, 0, 0));
-        }
-      }
-      g.mx[rg] = mv;   // (turned into the scale, and selected against `nv`, when it is consumed: nothing here may wait for the request)
-      g.nv[rg] = n;
-    }
+  // the quad-coalesced requests of one offset's rows (dense_tile.h), one offset ahead of their use.  (Two offsets ahead,
+  // with a second register set, measured 202 against 205 us on the 195 k-row 64 -> 64 layers at 230 against 176 VGPRs:
+  // the gather is bounded by the memory system's rate for random 256-byte rows beyond the L2
+  // (tools/microbench/vmem_bw.hip), not by latency.)
+  using Rows = DenseTileRows<RG, S>;
+  auto gather = [&](int k, Rows &g) {
+    dense_tile_request<RG, S, PS>(g, [&](int rg) { return nbr_s[k][(wave * RG + rg) * 16 + (lane >> 2)]; }, lane, in_rsrc, a, 0u);
   };
-  // offsets the row requests run ahead (one register set each).  Measured on the 195 k-row 64 -> 64 layers: depth 2
-  // (230 VGPRs) 202 us, depth 1 (176 VGPRs) 205 us -- the gather is bounded by the memory system's rate for random
-  // 256-byte rows beyond the L2 (tools/microbench/vmem_bw.hip), not by latency
-  constexpr int DEPTH = 1;
-  static_assert(DEPTH == 1 || DEPTH == 2, "prefetch depth");
-  RowSet gA, gB;
+  Rows gA;
   gather(0, gA);
-  if (DEPTH == 2) gather(1, gB);
 #pragma unroll
   for (int i = 0; i < WD; ++i) wreq(i, i);
   const int relu_lo = a.in_relu ? 0 : (int)0x80000000;   // pending ReLU of the producer as one integer max per value
 
-  auto body = [&](int k, RowSet &g) {
-    // ---- operands of this offset: s x = h + m, two f16 pieces (dgr_split2), in MFMA B layout
+  auto body = [&](int k, Rows &g) {
+    // ---- operands of this offset: s x = h + m, two f16 pieces, in MFMA B layout (dense_tile_operand);
+    //      fold[rg] = 2^-e(row, k) / weight scale of the row this lane ACCUMULATES (lane & 15), zero for a missing one
     f16x8 bh[RG][S], bm[RG][S];
     float fold[RG];
-    // lane T = 16 lq + lr of the operand layout takes from lane 4 lr + lq of the request layout
     const int from = 4 * (4 * (lane & 15) + (lane >> 4));
 #pragma unroll
     for (int rg = 0; rg < RG; ++rg) {
@@ -202,39 +157,14 @@ __global__ void __launch_bounds__(64 * WAVES, 2) sparse_conv_dense_f16x2(ConvDen
       const float fl = sx != 0.f ? dgr_inv_pow2(sx) * a.w_unscale : 0.f;
       fold[rg] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(16 * (lane & 15), __builtin_bit_cast(int, fl)));
 #pragma unroll
-      for (int s = 0; s < S; ++s) {
-        i32x4 hw, mw;   // four dwords = eight halves each: elements 0..3 from the first request, 4..7 from the second
-        if constexpr (PS) {
-          hw = __builtin_bit_cast(i32x4, g.raw[rg][s][0]);
-          mw = __builtin_bit_cast(i32x4, g.raw[rg][s][1]);
-        } else
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const i32x4 v = __builtin_bit_cast(i32x4, g.raw[rg][s][h]);
-#pragma unroll
-          for (int u = 0; u < 4; u += 2) {
-            const f32x2 xs = f32x2{__builtin_bit_cast(float, max(v[u], relu_lo)), __builtin_bit_cast(float, max(v[u + 1], relu_lo))} * sx;
-            const f16x2 hh = __builtin_convertvector(xs, f16x2);
-            const f16x2 mm = __builtin_convertvector(xs - __builtin_convertvector(hh, f32x2), f16x2);
-            hw[2 * h + u / 2] = __builtin_bit_cast(int, hh);
-            mw[2 * h + u / 2] = __builtin_bit_cast(int, mm);
-          }
-        }
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          hw[d] = __builtin_amdgcn_ds_bpermute(from, hw[d]);
-          mw[d] = __builtin_amdgcn_ds_bpermute(from, mw[d]);
-        }
-        bh[rg][s] = __builtin_bit_cast(f16x8, hw);
-        bm[rg][s] = __builtin_bit_cast(f16x8, mw);
-      }
+      for (int s = 0; s < S; ++s) dense_tile_operand<PS>(g.raw[rg][s][0], g.raw[rg][s][1], from, relu_lo, sx, bh[rg][s], bm[rg][s]);
     }
     __builtin_amdgcn_sched_barrier(0);   // operands complete before the raw registers are re-requested (else the scheduler
                                          // keeps both generations alive and a register-pair false dependency makes the
                                          // conversions wait for the NEW requests)
     // ---- next offset's rows requested; they arrive during this offset's MFMAs (the weight ring is refilled step by
     //      step below: in the in-order memory counter every ring slot is older than the rows requested after it)
-    gather(min(k + DEPTH, KV - 1), g);   // refills the set just consumed
+    gather(min(k + 1, KV - 1), g);   // refills the set just consumed
     __builtin_amdgcn_sched_barrier(0);   // (the scheduler otherwise sinks these requests below the MFMAs: no time in flight)
     // ---- this offset's tiles, one 16-column block after the other: tmp = W[k]^T x (zero for missing neighbours), folded
     //      into the running total one block late -- nothing waits for the matrix pipe.  Per 32-channel step: its MFMAs,
@@ -252,12 +182,7 @@ __global__ void __launch_bounds__(64 * WAVES, 2) sparse_conv_dense_f16x2(ConvDen
         const int j = cb * S + s;
         const f16x8 wh = __builtin_bit_cast(f16x8, rh[j % WD]);
         const f16x8 wm = __builtin_bit_cast(f16x8, rm[j % WD]);
-#pragma unroll
-        for (int rg = 0; rg < RG; ++rg) tmp[rg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wm, bh[rg][s], tmp[rg], 0, 0, 0);
-#pragma unroll
-        for (int rg = 0; rg < RG; ++rg) tmp[rg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bm[rg][s], tmp[rg], 0, 0, 0);
-#pragma unroll
-        for (int rg = 0; rg < RG; ++rg) tmp[rg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bh[rg][s], tmp[rg], 0, 0, 0);
+        dense_tile_mfma(tmp, wh, wm, bh, bm, s);
         wreq(k * NST + j + WD, j % WD);   // the ring slot just consumed
         if (s == 0 && cb > 0) {
 #pragma unroll
@@ -271,69 +196,29 @@ __global__ void __launch_bounds__(64 * WAVES, 2) sparse_conv_dense_f16x2(ConvDen
 #pragma unroll
     for (int rg = 0; rg < RG; ++rg) total[rg][NCB - 1] += prev[rg] * fold[rg];
   };
-  if (DEPTH == 1) {
 #pragma unroll 1
-    for (int k = 0; k < KV; ++k) body(k, gA);
-  } else {
-#pragma unroll 1
-    for (int k = 0; k < KV - 1; k += 2) {
-      body(k, gA);
-      body(k + 1, gB);
-    }
-    body(KV - 1, gA);
-  }
+  for (int k = 0; k < KV; ++k) body(k, gA);
 
-  // ---- the rows are written once (ReLU applied here when the tensor carries one)
-  //      ... and their largest |x| is left behind for the split-operand consumers of this tensor: a row's channels sit
-  //      in the four lanes lr + 16 lq of this wave
-  const float out_lo = a.out_relu ? 0.f : -__builtin_inff();
+  // ---- the rows are written once, and their largest |x| is left behind (dense_tile.h)
   const int out_relu_lo = a.out_relu ? 0 : (int)0x80000000;
 #pragma unroll
   for (int rg = 0; rg < RG; ++rg) {
-    const int64_t row = row0 + (wave * RG + rg) * 16 + lr;
-    uint32_t mx = 0;
-#pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
-      f32x4 v = total[rg][cb];
-      v.x = fmaxf(v.x, out_lo); v.y = fmaxf(v.y, out_lo); v.z = fmaxf(v.z, out_lo); v.w = fmaxf(v.w, out_lo);
-      total[rg][cb] = v;
-      if (row < n_out) {
-        if (a.out) *reinterpret_cast<f32x4 *>(a.out + row * a.out_ld + 16 * cb + 4 * lq) = v;
-        const i32x4 b = __builtin_bit_cast(i32x4, v);
-        mx = max(mx, max(max((uint32_t)b.x & 0x7fffffffu, (uint32_t)b.y & 0x7fffffffu), max((uint32_t)b.z & 0x7fffffffu, (uint32_t)b.w & 0x7fffffffu)));
-      }
-    }
-    if (a.out_amax || a.out_amax2 || a.out_ds) {   // (kernel-uniform)
-      mx = max(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
-      mx = max(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
-      if (lq == 0 && row < n_out) {
-        if (a.out_amax) atomicMax(a.out_amax + row, mx);
-        if (a.out_amax2) atomicMax(a.out_amax2 + row, mx);
-      }
-    }
-    if (a.out_ds && row < n_out) {
+    const int64_t r = row0 + (wave * RG + rg) * 16 + lr;
+    const int64_t row = r < n_out ? r : -1;
+    const uint32_t mx = dense_tile_store_row(total[rg], row, a.out ? a.out + 4 * lq : nullptr, a.out_ld, a.out_relu, lq,
+                                             a.out_amax || a.out_amax2 || a.out_ds, a.out_amax, a.out_amax2);
+    if (a.out_ds && row >= 0) {
       // the row once more as the next dense-tile layer's operands: exactly what that layer's own split makes of the f32
-      // row (the row's scale from the same maximum, the pending ReLU as the same integer max, dgr_split2's roundings);
+      // row (the row's scale from the same maximum, the pending ReLU as the same integer max, the same dgr_split2_x8);
       // lane (lr, lq) holds chunk lq of every 32-channel group: channels 4 lq .. + 3 of column blocks 2 s and 2 s + 1
       const float sx = dgr_row_scale_of(mx);
       unsigned char *dst = a.out_ds + row * (int64_t)(4 * COUT) + 16 * lq;
 #pragma unroll
       for (int s = 0; s < COUT / 32; ++s) {
-        u32x4 hw, mw;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const i32x4 v = __builtin_bit_cast(i32x4, total[rg][2 * s + h]);
-#pragma unroll
-          for (int u = 0; u < 4; u += 2) {
-            const f32x2 xs = f32x2{__builtin_bit_cast(float, max(v[u], out_relu_lo)), __builtin_bit_cast(float, max(v[u + 1], out_relu_lo))} * sx;
-            const f16x2 hh = __builtin_convertvector(xs, f16x2);
-            const f16x2 mm = __builtin_convertvector(xs - __builtin_convertvector(hh, f32x2), f16x2);
-            hw[2 * h + u / 2] = __builtin_bit_cast(uint32_t, hh);
-            mw[2 * h + u / 2] = __builtin_bit_cast(uint32_t, mm);
-          }
-        }
-        *reinterpret_cast<u32x4 *>(dst + 64 * s) = hw;
-        *reinterpret_cast<u32x4 *>(dst + 2 * COUT + 64 * s) = mw;
+        i32x4 hw, mw;
+        dgr_split2_x8(__builtin_bit_cast(i32x4, total[rg][2 * s]), __builtin_bit_cast(i32x4, total[rg][2 * s + 1]), out_relu_lo, sx, hw, mw);
+        *reinterpret_cast<i32x4 *>(dst + 64 * s) = hw;
+        *reinterpret_cast<i32x4 *>(dst + 2 * COUT + 64 * s) = mw;
       }
     }
   }
@@ -360,21 +245,13 @@ static int launch_dense(const ConvDenseArgs &ka, int64_t n_out_cap, hipStream_t 
 int dgr_conv_dense_launch(const DgrConvOsLaunch &a, hipStream_t stream, const char **kernel_name) {
   DGR_REQUIRE(a.nbr && a.nbr->built && a.nbr->K == 27, "dense-tile conv: no neighbour table");
   DGR_REQUIRE(dgr_conv_dense_supported(a.cin, a.cin_pad, a.cout), "dense-tile conv: Cin = %d, Cout = %d not built", a.cin, a.cout);
-  DGR_REQUIRE(a.wbd && a.row_amax, "dense-tile conv: needs the split weights in its operand order and the input rows' maxima");
-  DGR_REQUIRE((a.in_ld & 3) == 0 && (a.out_ld & 3) == 0 && (a.res == nullptr || (a.res_ld & 3) == 0),
-              "dense-tile conv: row strides must be multiples of 4");
-  ConvDenseArgs ka;
-  ka.in = a.in; ka.out = a.out; ka.shift = a.shift; ka.res = a.res;
-  ka.wb = static_cast<const u32x4 *>(a.wbd); ka.piece_stride = a.piece_stride;
-  ka.nbr = a.nbr->nbr; ka.n_out_dev = a.n_out_dev; ka.n_pad = a.nbr->n_pad;
-  ka.in_ld = a.in_ld; ka.in_relu = a.in_relu; ka.out_ld = a.out_ld; ka.out_relu = a.out_relu;
-  ka.res_ld = a.res_ld; ka.res_relu = a.res_relu;
-  ka.row_amax = a.row_amax; ka.w_unscale = a.w_unscale;
-  ka.out_amax = a.out_amax; ka.out_amax2 = a.out_amax2;
-  ka.in_ds = a.in_dsplit; ka.out_ds = a.out_dsplit;
   DGR_REQUIRE(a.out || a.out_dsplit, "dense-tile conv: no output");
-  DGR_REQUIRE(a.n_in_cap > 0 && a.n_in_cap * (int64_t)a.in_ld * 4 < (1ll << 31), "dense-tile conv: input tensor beyond 2 GB");
-  ka.in_bytes = (uint32_t)(a.n_in_cap * (int64_t)(a.in_dsplit ? a.cin : a.in_ld) * 4);
+  ConvDenseArgs ka;
+  if (const int rc = dgr_dense_tile_args(ka, a, "dense-tile conv")) return rc;
+  ka.res = a.res; ka.res_ld = a.res_ld; ka.res_relu = a.res_relu;
+  ka.n_out_dev = a.n_out_dev;
+  ka.in_ds = a.in_dsplit; ka.out_ds = a.out_dsplit;
+  if (a.in_dsplit) ka.in_bytes = (uint32_t)(a.n_in_cap * (int64_t)a.cin * 4);   // (dense split rows: 4 Cin bytes each)
 #define DGR_DENSE(CI, CO)                                                                   \
   if (a.cin == CI && a.cout == CO) {                                                        \
     if (kernel_name) *kernel_name = a.in_dsplit ? "sparse_conv_dense_f16x2<" #CI ", " #CO ", ps>" : "sparse_conv_dense_f16x2<" #CI ", " #CO ">"; \

@@ -33,13 +33,6 @@
 #include "dgr_internal.h"
 #include "split.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 #ifdef DGR_OS_STAGE_CLK
 // tools/os_stage_clk.py (build with EXTRA=-DDGR_OS_STAGE_CLK): per-workgroup wall-clock sums of the kernel's stages --
 // [0] list compaction, [1] accumulator init + group list, [2] the phases, [3] epilogue, [4] workgroups, [5] phases
@@ -363,12 +356,10 @@ __global__ void __launch_bounds__(CS * 4 * (TM / 16 / GW)) sparse_conv_os(ConvOs
       f32x4 v = *reinterpret_cast<const f32x4 *>(&acc_s[r][c]);
       v.x = fmaxf(v.x, out_lo); v.y = fmaxf(v.y, out_lo); v.z = fmaxf(v.z, out_lo); v.w = fmaxf(v.w, out_lo);
       *reinterpret_cast<f32x4 *>(a.out + (row0 + r) * a.out_ld + slice * CS + c) = v;
-      const i32x4 b = __builtin_bit_cast(i32x4, v);
-      mx = max(max((uint32_t)b.x & 0x7fffffffu, (uint32_t)b.y & 0x7fffffffu), max((uint32_t)b.z & 0x7fffffffu, (uint32_t)b.w & 0x7fffffffu));
+      mx = dgr_abs_max4(__builtin_bit_cast(i32x4, v));
     }
     if (a.out_amax || a.out_amax2) {   // (kernel-uniform)
-#pragma unroll
-      for (int d = CS / 8; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+      mx = dgr_lane_max<CS / 4>(mx);
       if (live && (e % (CS / 4)) == 0 && row0 + r < n_out) {
         if (a.out_amax) atomicMax(a.out_amax + row0 + r, mx);
         if (a.out_amax2) atomicMax(a.out_amax2 + row0 + r, mx);

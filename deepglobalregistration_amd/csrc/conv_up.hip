@@ -11,11 +11,12 @@
 //
 //   * the neighbour search (kmap.hip, nbr_search3) leaves the output rows grouped by class (DgrNbrTable::perm);
 //   * a workgroup takes MB rows of ONE class and walks only that class's offsets, in ascending k (the summation order
-//     of every other kernel of this layer family), as DENSE tiles: the dense-tile kernel's structure (conv_dense.hip:
-//     quad-coalesced gather of the neighbours' f32 rows through bounds-checked buffer loads, split into the two f16
-//     pieces in registers, ds_bpermute into MFMA operand order, weights through a per-wave register ring straight from
-//     L2, accumulators in registers, no LDS tile, no lists, no barrier in the loop) with the input channels taken 64 at
-//     a time (Cin = 128 | 256) and the output channels in slices of 64 (blockIdx.y);
+//     of every other kernel of this layer family), as DENSE tiles, built from the dense-tile pieces of dense_tile.h that
+//     conv_dense.hip uses too (quad-coalesced gather of the neighbours' f32 rows through bounds-checked buffer loads,
+//     split into the two f16 pieces in registers, ds_bpermute into MFMA operand order, the three-product MFMA step, the
+//     row epilogue) around a weight ring of its own (per wave, straight from L2): accumulators in registers, no LDS tile,
+//     no lists, no barrier in the loop, with the input channels taken 64 at a time (Cin = 128 | 256) and the output
+//     channels in slices of 64 (blockIdx.y);
 //   * per (row, offset) the same arithmetic as conv_dense.hip / conv_os.hip: tmp = sum over the 32-channel steps of
 //     w_m x_h + w_h x_m + w_h x_h (f32 accumulate in the MFMA), total += tmp * 2^-e(row) / weight scale, on top of the
 //     folded batch-norm shift.  Results agree with the list-based kernel to a few f32 ulps of the tensor's scale (the
@@ -23,32 +24,12 @@
 //
 // Weights: the layer's split pieces in the dense-tile kernel's operand order (net.hip, w16d),
 // [piece][k][Cin / 32][Cout / 16][lane] x 16 bytes.
-#include "dgr_internal.h"
-#include "split.h"
+#include "dense_tile.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-struct ConvUpArgs {
-  const float *in;
-  float *out;
-  const float *shift;
-  const u32x4 *wb;
-  int64_t piece_stride;      // 16-byte units per piece
-  const int32_t *nbr;
-  int64_t n_pad;
+struct ConvUpArgs : DenseTileArgs {
   const int32_t *perm, *cls_count;
   int64_t cls_cap;
-  int in_ld, in_relu, out_ld, out_relu;
   int nb16;                  // Cout / 16 of the whole layer
-  const uint32_t *row_amax;
-  uint32_t *out_amax, *out_amax2;
-  float w_unscale;
-  uint32_t in_bytes;
 };
 
 // CIN in {128, 256}; a workgroup writes a 64-channel slice of MB = WAVES x RG x 16 rows of one parity class
@@ -127,36 +108,24 @@ __global__ void __launch_bounds__(64 * WAVES, 2) sparse_conv_up_f16x2(ConvUpArgs
   __syncthreads();
 
   const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, a.in_bytes, 0x00020000);
-  struct RowSet { f32x4 raw[RG][2][2]; uint32_t mx[RG]; int nv[RG]; };
-  // quad-coalesced request layout (conv_dense.hip): lane 4 r + c reads 16 bytes of row r
-  auto gather = [&](int it, RowSet &g) {
+  // the quad-coalesced requests (dense_tile.h) of 64-channel chunk ch of the rows under offset li
+  DenseTileRows<RG, 2> gA;
+  auto gather = [&](int it) {
     const int li = it / NCH, ch = it - li * NCH;
-#pragma unroll
-    for (int rg = 0; rg < RG; ++rg) {
-      const int n = nbr_s[li][(wave * RG + rg) * 16 + (lane >> 2)];
-      const int ne = max(n, 0);
-      const uint32_t off = n >= 0 ? (uint32_t)n * (uint32_t)(a.in_ld * 4) + 256u * ch + 16u * (lane & 3) : a.in_bytes;
-      const uint32_t mv = a.row_amax[ne];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        g.raw[rg][s][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off + 128 * s, 0, 0));
-        g.raw[rg][s][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off + 128 * s + 64, 0, 0));
-      }
-      g.mx[rg] = mv;
-      g.nv[rg] = n;
-    }
+    dense_tile_request<RG, 2, false>(gA, [&](int rg) { return nbr_s[li][(wave * RG + rg) * 16 + (lane >> 2)]; }, lane, in_rsrc,
+                                     a, 256u * ch);
   };
-  RowSet gA;
-  gather(0, gA);
+  gather(0);
 #pragma unroll
   for (int i = 0; i < WD; ++i) wreq(i, i);
   const int relu_lo = a.in_relu ? 0 : (int)0x80000000;
 
-  f32x4 tmp[RG][NCB];
+  f32x4 tmp[NCB][RG];
 #pragma unroll 1
   for (int it = 0; it < NIT; ++it) {
     const int ch = it % NCH;
-    // ---- operands of this (offset, chunk): s x = h + m, two f16 pieces (dgr_split2), in MFMA B layout
+    // ---- operands of this (offset, chunk): s x = h + m, two f16 pieces, in MFMA B layout (dense_tile_operand);
+    //      fold[rg] = 2^-e(row) / weight scale of the row this lane ACCUMULATES (lane & 15), zero for a missing one
     f16x8 bh[RG][2], bm[RG][2];
     float fold[RG];
     const int from = 4 * (4 * (lane & 15) + (lane >> 4));
@@ -166,37 +135,16 @@ __global__ void __launch_bounds__(64 * WAVES, 2) sparse_conv_up_f16x2(ConvUpArgs
       const float fl = sx != 0.f ? dgr_inv_pow2(sx) * a.w_unscale : 0.f;
       fold[rg] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(16 * (lane & 15), __builtin_bit_cast(int, fl)));
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        i32x4 hw, mw;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const i32x4 v = __builtin_bit_cast(i32x4, gA.raw[rg][s][h]);
-#pragma unroll
-          for (int u = 0; u < 4; u += 2) {
-            const f32x2 xs = f32x2{__builtin_bit_cast(float, max(v[u], relu_lo)), __builtin_bit_cast(float, max(v[u + 1], relu_lo))} * sx;
-            const f16x2 hh = __builtin_convertvector(xs, f16x2);
-            const f16x2 mm = __builtin_convertvector(xs - __builtin_convertvector(hh, f32x2), f16x2);
-            hw[2 * h + u / 2] = __builtin_bit_cast(int, hh);
-            mw[2 * h + u / 2] = __builtin_bit_cast(int, mm);
-          }
-        }
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          hw[d] = __builtin_amdgcn_ds_bpermute(from, hw[d]);
-          mw[d] = __builtin_amdgcn_ds_bpermute(from, mw[d]);
-        }
-        bh[rg][s] = __builtin_bit_cast(f16x8, hw);
-        bm[rg][s] = __builtin_bit_cast(f16x8, mw);
-      }
+      for (int s = 0; s < 2; ++s) dense_tile_operand<false>(gA.raw[rg][s][0], gA.raw[rg][s][1], from, relu_lo, sx, bh[rg][s], bm[rg][s]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    gather(min(it + 1, NIT - 1), gA);
+    gather(min(it + 1, NIT - 1));
     __builtin_amdgcn_sched_barrier(0);
     if (ch == 0) {
 #pragma unroll
       for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) tmp[rg][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int cb = 0; cb < NCB; ++cb) tmp[cb][rg] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
@@ -205,12 +153,7 @@ __global__ void __launch_bounds__(64 * WAVES, 2) sparse_conv_up_f16x2(ConvUpArgs
         const int j = cb * 2 + s;
         const f16x8 wh = __builtin_bit_cast(f16x8, rh[j]);
         const f16x8 wm = __builtin_bit_cast(f16x8, rm[j]);
-#pragma unroll
-        for (int rg = 0; rg < RG; ++rg) tmp[rg][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wm, bh[rg][s], tmp[rg][cb], 0, 0, 0);
-#pragma unroll
-        for (int rg = 0; rg < RG; ++rg) tmp[rg][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bm[rg][s], tmp[rg][cb], 0, 0, 0);
-#pragma unroll
-        for (int rg = 0; rg < RG; ++rg) tmp[rg][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bh[rg][s], tmp[rg][cb], 0, 0, 0);
+        dense_tile_mfma(tmp[cb], wh, wm, bh, bm, s);
         wreq((it + 1) * NST + j, j);   // the ring slot just consumed: the same step of the next (offset, chunk)
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -219,34 +162,16 @@ __global__ void __launch_bounds__(64 * WAVES, 2) sparse_conv_up_f16x2(ConvUpArgs
 #pragma unroll
       for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) total[rg][cb] += tmp[rg][cb] * fold[rg];
+        for (int cb = 0; cb < NCB; ++cb) total[rg][cb] += tmp[cb][rg] * fold[rg];
     }
   }
 
-  // ---- the rows are written once, through the class's row list
-  const float out_lo = a.out_relu ? 0.f : -__builtin_inff();
+  // ---- the rows are written once, through the class's row list (dense_tile.h)
 #pragma unroll
   for (int rg = 0; rg < RG; ++rg) {
     const int64_t row = rows_s[(wave * RG + rg) * 16 + lr];
-    uint32_t mx = 0;
-    if (row >= 0) {
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) {
-        f32x4 v = total[rg][cb];
-        v.x = fmaxf(v.x, out_lo); v.y = fmaxf(v.y, out_lo); v.z = fmaxf(v.z, out_lo); v.w = fmaxf(v.w, out_lo);
-        *reinterpret_cast<f32x4 *>(a.out + row * a.out_ld + 64 * slice + 16 * cb + 4 * lq) = v;
-        const i32x4 b = __builtin_bit_cast(i32x4, v);
-        mx = max(mx, max(max((uint32_t)b.x & 0x7fffffffu, (uint32_t)b.y & 0x7fffffffu), max((uint32_t)b.z & 0x7fffffffu, (uint32_t)b.w & 0x7fffffffu)));
-      }
-    }
-    if (a.out_amax || a.out_amax2) {   // (kernel-uniform)
-      mx = max(mx, (uint32_t)__shfl_xor((int)mx, 16, 64));
-      mx = max(mx, (uint32_t)__shfl_xor((int)mx, 32, 64));
-      if (lq == 0 && row >= 0) {
-        if (a.out_amax) atomicMax(a.out_amax + row, mx);
-        if (a.out_amax2) atomicMax(a.out_amax2 + row, mx);
-      }
-    }
+    dense_tile_store_row(total[rg], row, a.out + 64 * slice + 4 * lq, a.out_ld, a.out_relu, lq, a.out_amax || a.out_amax2, a.out_amax,
+                         a.out_amax2);
   }
 }
 
@@ -258,20 +183,11 @@ int dgr_conv_up_launch(const DgrConvOsLaunch &a, hipStream_t stream, const char 
   DGR_REQUIRE(a.nbr && a.nbr->built && a.nbr->K == 27 && a.nbr->perm && a.nbr->cls_count,
               "parity-class transposed conv: no neighbour table with a class row list");
   DGR_REQUIRE(dgr_conv_up_supported(a.cin, a.cin_pad, a.cout), "parity-class transposed conv: Cin = %d, Cout = %d not built", a.cin, a.cout);
-  DGR_REQUIRE(a.wbd && a.row_amax, "parity-class transposed conv: needs the split weights in the dense-tile operand order and the input rows' maxima");
   DGR_REQUIRE(a.res == nullptr, "parity-class transposed conv: no residual input");
-  DGR_REQUIRE((a.in_ld & 3) == 0 && (a.out_ld & 3) == 0, "parity-class transposed conv: row strides must be multiples of 4");
-  DGR_REQUIRE(a.n_in_cap > 0 && a.n_in_cap * (int64_t)a.in_ld * 4 < (1ll << 31), "parity-class transposed conv: input tensor beyond 2 GB");
   ConvUpArgs ka;
-  ka.in = a.in; ka.out = a.out; ka.shift = a.shift;
-  ka.wb = static_cast<const u32x4 *>(a.wbd); ka.piece_stride = a.piece_stride;
-  ka.nbr = a.nbr->nbr; ka.n_pad = a.nbr->n_pad;
+  if (const int rc = dgr_dense_tile_args(ka, a, "parity-class transposed conv")) return rc;
   ka.perm = a.nbr->perm; ka.cls_count = a.nbr->cls_count; ka.cls_cap = a.nbr->cls_cap;
-  ka.in_ld = a.in_ld; ka.in_relu = a.in_relu; ka.out_ld = a.out_ld; ka.out_relu = a.out_relu;
   ka.nb16 = a.cout / 16;
-  ka.row_amax = a.row_amax; ka.out_amax = a.out_amax; ka.out_amax2 = a.out_amax2;
-  ka.w_unscale = a.w_unscale;
-  ka.in_bytes = (uint32_t)(a.n_in_cap * (int64_t)a.in_ld * 4);
   // (64-row workgroups at the coarse levels measured no better: 63 against 60-70 us for conv4_tr, tools/r06_runs/run24.sh)
   constexpr int RG = 2, WAVES = 4, MB = WAVES * RG * 16;
   // (eight classes, each rounded up to whole workgroups)

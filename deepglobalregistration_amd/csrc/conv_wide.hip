@@ -54,10 +54,6 @@
 #include "dgr_internal.h"
 #include "split.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct ConvWideArgs {
   const unsigned char *planes;   // split input rows, 4 CP bytes per row (layout above)
   const float *row_scale;        // power-of-two scale per input row
@@ -440,9 +436,6 @@ int dgr_conv_wide_launch(const DgrConvLaunch &a, const DgrSplitRows &in, const v
 // Row maxima / split rows of an EXISTING f32 tensor.  On the network path the producers leave both behind themselves
 // (reduce_rows in conv.hip; the epilogues of conv_os.hip / conv_dense.hip / the conv1 kernels); these serve the
 // single-layer debug entry point and inputs that did not come out of one of those kernels.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 // LPR = lanes per row (16 bytes each; wider rows loop): largest |x| (after the pending ReLU) -> the power of two that
 // moves it into [2^14, 2^15); SPLIT: also the row's two f16 planes.  A wave covers 64 / LPR rows at a time.
 template <int LPR, bool SPLIT>
@@ -461,13 +454,10 @@ __global__ void __launch_bounds__(256) row_scale_kernel(const float *__restrict_
     if (r < n) {
       const float *row = in + r * in_ld;
       for (int c = l * 4; c < cin; c += LPR * 4) {
-        const i32x4 v = __builtin_bit_cast(i32x4, *reinterpret_cast<const f32x4 *>(row + c));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) mx = max(mx, (uint32_t)max(v[u], relu_lo) & 0x7fffffffu);   // |x| as an integer
+        mx = max(mx, dgr_abs_max4(__builtin_bit_cast(i32x4, *reinterpret_cast<const f32x4 *>(row + c)), relu_lo));
       }
     }
-#pragma unroll
-    for (int d = LPR / 2; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
+    mx = dgr_lane_max<LPR>(mx);
     const float sx = dgr_row_scale_of(mx);
     if (l == 0 && r < n) {
       if (out) out[r] = sx;

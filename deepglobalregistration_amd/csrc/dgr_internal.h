@@ -273,6 +273,9 @@ struct DgrConvOsLaunch {
   const unsigned char *in_dsplit = nullptr;
   unsigned char *out_dsplit = nullptr;
 };
+// a tensor of `rows` rows of `ld` floats is addressable by 32-bit byte offsets (the buffer loads of the dense-tile
+// kernels): it is smaller than 2 GB
+inline bool dgr_fits_32bit_offsets(int64_t rows, int64_t ld) { return rows * ld * 4 < (1ll << 31); }
 int dgr_conv_os_launch(const DgrConvOsLaunch &a, hipStream_t stream, const char **kernel_name = nullptr);
 bool dgr_conv_dense_supported(int cin, int cin_pad, int cout);
 int dgr_conv_dense_launch(const DgrConvOsLaunch &a, hipStream_t stream, const char **kernel_name = nullptr);

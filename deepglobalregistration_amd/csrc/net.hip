@@ -578,12 +578,12 @@ struct Fwd {
       for (int l = 0; l < 4; ++l) same_stride = same_stride || t == &ms.nsame[l];
       // (its buffer loads address the input with 32-bit byte offsets: tensors of 2 GB and more stay on the list kernel)
       o.dense = same_stride && o.row_amax && o.wbd && !os_lists && dgr_conv_dense_supported(L.cin, L.cin_pad, L.cout) &&
-                cin_map.n_cap * (int64_t)in.ld * 4 < (1ll << 31);
+                dgr_fits_32bit_offsets(cin_map.n_cap, in.ld);
       DGR_REQUIRE(o.dense || (!in.dsplit_only && !out.dsplit_only), "layer %s: dense split rows outside the dense-tile kernel", L.name.c_str());
       // transposed convs (the strided map used swapped) with Cin, Cout multiples of 64: by parity class of the output rows
       static const bool no_up = getenv("DGR_NO_UP") != nullptr;   // A/B
       o.up = swapped && !o.dense && !no_up && !os_lists && o.row_amax && o.wbd && t->perm && res == nullptr &&
-             dgr_conv_up_supported(L.cin, L.cin_pad, L.cout) && cin_map.n_cap * (int64_t)in.ld * 4 < (1ll << 31);
+             dgr_conv_up_supported(L.cin, L.cin_pad, L.cout) && dgr_fits_32bit_offsets(cin_map.n_cap, in.ld);
       if (o.dense) {
         o.in_dsplit = in.dsplit;
         o.out_dsplit = out.dsplit;
@@ -767,7 +767,7 @@ int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, 
     auto dense_layer = [&](int l, int64_t rows) {
       const DgrLayer &L = net->W->layers[l];
       return L.w16b && L.w16d && !dgr_exact_f32() && !os_lists && dgr_conv_dense_supported(L.cin, L.cin_pad, L.cout) &&
-             rows * (int64_t)L.cin * 4 < (1ll << 31);
+             dgr_fits_32bit_offsets(rows, L.cin);
     };
     struct { Tensor *t; int producer; int64_t rows; } mid[] = {{&Y1, 1, n1}, {&Y2, 4, n2}, {&V2, 16, n2}, {&V1, 19, n1}};
     for (auto &e : mid)

@@ -1,14 +1,20 @@
 #!/usr/bin/env python
 """Per-layer timing of the sparse conv on the benchmark workload (one 50k-pt pair): for each conv of
 the 6-D inlier net and of the 3-D FCGF net prints pairs, shape, GFLOP, MFMA-phase and reduce-phase
-time, TFLOP/s and the implied GB/s of the gather + product-row traffic.  Kernel-tuning instrument."""
-import os, sys
+time, TFLOP/s and the implied GB/s of the gather + product-row traffic.  Kernel-tuning instrument.
+
+    python tools/layer_bench.py [LAYERS|all] [RERUNS]
+
+LAYERS: comma-separated layer numbers; RERUNS > 0: after the warm-up rerun of five, time every layer RERUNS times one by
+one and print the median (min-max) and the sorted samples of the MFMA-phase time (the A/B records of profiles/)."""
+import os, statistics, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepglobalregistration_amd import ops, synth
 from deepglobalregistration_amd.core.deep_global_registration import DeepGlobalRegistration
 
-layers = [int(x) for x in sys.argv[1].split(',')] if len(sys.argv) > 1 else None
+layers = [int(x) for x in sys.argv[1].split(',')] if len(sys.argv) > 1 and sys.argv[1] != 'all' else None
+reruns = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 ck = synth.synth_checkpoint(0)
 dgr = DeepGlobalRegistration({'weights': ck}, torch.device('cuda'))
 x0, x1, T = synth.synth_pair(0, 50000)
@@ -37,6 +43,10 @@ for name, net, args in (('6-D', dgr.inlier_model._handle(), (c6, f6)), ('3-D', d
         fl = 2.0 * s['pairs'] * s['cin'] * s['cout']
         gb = 4.0 * s['pairs'] * s['cin']
         yb = 4.0 * s['pairs'] * s['cout']
+        if reruns > 0:
+            us = sorted(net.rerun_layer(li, 1)[0] * 1e3 for _ in range(reruns))
+            g = statistics.median(us) * 1e-3
+            print(f"{li:2d} gemm_us median {g * 1e3:.2f} ({us[0]:.1f}-{us[-1]:.1f}) of {reruns}: " + ' '.join(f'{u:.2f}' for u in us))
         tot_g += g; tot_r += r
         print(f"{li:2d} {s['pairs']:8d} {s['nonempty']:4d} {s['n_in']:6d} {s['n_out']:6d} {s['cin']:4d} {s['cout']:4d} | "
               f"{fl / 1e9:7.2f} {g * 1e3:8.1f} {r * 1e3:8.1f} {fl / (g * 1e-3) / 1e12:6.1f} {gb / (g * 1e-3) / 1e9:8.0f} {yb / (g * 1e-3) / 1e9:8.0f}")
