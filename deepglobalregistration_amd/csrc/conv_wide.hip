@@ -25,21 +25,27 @@
 // per CU walks an XCD-aware share of the tiles (block b runs on XCD b % 8; an XCD gets a contiguous range of offsets, so
 // a weight slice lives in one L2).  Work is split by latency domain, because s_waitcnt vmcnt retires loads AND stores
 // in order -- a wave that gathers, loads weights and stores waits for all three whenever it waits for one:
-//   * waves 0..3 (compute): their only memory operations are weight fragments -- a register ring WD k-steps deep (2;
-//     4 for the 64-channel-output shape, whose k-steps are three MFMAs long), NB x 2 16-byte loads per k-step,
-//     unconditional, every wait count static -- then 3 MB NB v_mfma_f32_32x32x16_f16 per k-step on the landed planes
-//     (the next k-step's operands are prefetched from LDS, across the phase barrier too).  Two accumulator sets
+//   * waves 0..3 (compute): their only memory operations are weight fragments -- a register ring, NB x 2 16-byte loads
+//     per k-step, unconditional, every wait count static -- then 3 MB NB v_mfma_f32_32x32x16_f16 per k-step on the landed
+//     planes (the next k-step's operands are prefetched from LDS, across the phase barrier too).  The ring: four k-steps
+//     for the shapes with one 32-channel output block per wave; for the C_out = 256 shapes (two blocks, twelve MFMAs per
+//     k-step) eight HALF steps -- one block's two pieces per slot, requested 3.5 k-steps ahead, the k-step's MFMAs run
+//     block by block; the m planes of the operands are single-buffered to make room (256 VGPRs, no scratch).  On a
+//     64-CU share next to three other contexts a ring of two whole steps left the compute waves waiting for weights 27 %
+//     of a phase, this one 9 % (profiles/wide_share_stage_clk.txt).  Two accumulator sets
 //     alternate: while tile t + 1 is multiplied, the finished tile t leaves its registers for an LDS stage, a few
 //     16-byte pieces per k-step, in the shadow of the MFMAs.  Wave w computes rows 32 MB (w / WN) .. and output
 //     channels 32 NB (w % WN) ..: WM = 1 (four column waves, 64 rows each) for C_out >= 128, WM = 2 (two row halves x
 //     two column waves) for C_out = 64.
 //   * waves 4, 5 (requesters): gather the split rows with plain 16-byte loads, NSET = 4 64-channel phases in flight
-//     through four register sets, into a ring of NBUF = 3 LDS phase buffers; they also keep the index ring (eight tiles
-//     ahead) and the scale ring.  (LDS-DMA gathers were measured here: ~200 cycles of issue per 1-KB piece, and one wave
+//     through four register sets, into a ring of NBUF = 3 LDS phase buffers; they also keep the index and scale rings,
+//     whose loads stay in registers for at least NSET phases before they are published where a tile has two or four
+//     phases (vmcnt retires in order: a publish one tile after its request drains the younger gathers).  (LDS-DMA gathers
+//     were measured here: ~200 cycles of issue per 1-KB piece, and one wave
 //     mixing DMA with ordinary loads drains vmcnt(0).)
 //   * waves 6, 7 (storers): the staged product rows to HBM as whole rows, non-temporal, RPH rows per phase so that the
 //     store stream is even; scaled back by the row's and the layer's inverse powers of two on the way.
-// One raw s_waitcnt lgkmcnt(0) + s_barrier per phase (all eight waves); 130 KB of LDS at C_out = 256.
+// One raw s_waitcnt lgkmcnt(0) + s_barrier per phase (all eight waves); 129 KB of LDS at C_out = 256.
 // What bounds it: the three streams through the CU's vector-memory path -- 4 bytes of weights per
 // MAC-column (L2), the gathered rows (beyond L2) and the product rows -- not the matrix pipe (MFMA busy 0.43).
 //
@@ -81,6 +87,48 @@ __device__ __forceinline__ void dgr_phase_barrier() {   // LDS traffic of this w
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+#ifdef DGR_WIDE_STAGE_CLK
+// tools/wide_stage_clk.py (build with EXTRA=-DDGR_WIDE_STAGE_CLK): where the phases of this kernel go, per shape and role.
+// Every wave sums in registers, on the shader clock, the time between reaching and leaving the phase barrier; the compute
+// waves also the wait for the weight fragments of every ring step, the requesters the time inside land() and rings().
+// Added to the table once per wave at the end of the kernel: no atomics inside the phase loop.  Row = shape (below), columns:
+//   0-3 compute: barrier, weight wait, life, waves   4-8 requesters: barrier, land, rings, life, waves
+//   9-11 storers: barrier, life, waves   12 phases (one compute wave per workgroup)   13 / 14 life of those waves on the
+//   shader clock / on the 100-MHz wall clock (the conversion)
+__device__ unsigned long long dgr_wide_stage_clk[6][16];
+extern "C" int dgr_debug_wide_stage_clk(unsigned long long *out96, int reset) {
+  if (out96 && hipMemcpyFromSymbol(out96, HIP_SYMBOL(dgr_wide_stage_clk), 96 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (reset) {
+    unsigned long long z[96] = {0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(dgr_wide_stage_clk), z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#define DGR_WIDE_CLK(...) __VA_ARGS__
+#define DGR_WIDE_NOW() ((unsigned long long)__builtin_amdgcn_s_memtime())
+#else
+#define DGR_WIDE_CLK(...)
+#endif
+// the phase barrier of a role; the instrumented build adds the time from "own LDS traffic done" to "released" to `waited`
+__device__ __forceinline__ void dgr_wide_barrier(unsigned long long &waited) {
+#ifdef DGR_WIDE_STAGE_CLK
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  const unsigned long long t = DGR_WIDE_NOW();
+  dgr_phase_barrier();
+  waited += DGR_WIDE_NOW() - t;
+#else
+  dgr_phase_barrier();
+#endif
+}
+__host__ __device__ constexpr int dgr_wide_shape_id(int cp, int nb, int wm) {   // row of the stage-clock table
+  return wm == 2 ? 0 : nb == 2 ? (cp == 128 ? 4 : 5) : cp == 64 ? 1 : cp == 128 ? 2 : 3;
+}
+__host__ __device__ constexpr int dgr_wide_lcm(int a, int b) {
+  int m = a;
+  while (m % b) m += a;
+  return m;
+}
+
 // product-row store passes of phase h of a tile (of PPT): the tile's NPASS passes spread over its first NSP phases
 __host__ __device__ constexpr int dgr_wide_passes(int h, int npass, int nsp) {
   return h < nsp ? npass / nsp + (h < npass % nsp ? 1 : 0) : 0;
@@ -91,7 +139,9 @@ __host__ __device__ constexpr int dgr_wide_pass_base(int h, int npass, int nsp) 
   return b;
 }
 
-template <int CP, int NB, int WM>
+// NSET = register sets of a requesting wave = gathered phases in flight; HD = depth of the compute waves' weight ring in
+// HALF k-steps (one 32-channel output block, both pieces: NB = 2 only), 0 = the ring of whole k-steps
+template <int CP, int NB, int WM, int NSET, int HD>
 __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a, const int4 *__restrict__ tdesc) {
   constexpr int NCW = 4;                 // compute waves
   constexpr int NP = 2, MB = 2 / WM, WN = NCW / WM, PW = 4, TM = 64, CK = 64, SK = CK / 16;
@@ -101,17 +151,27 @@ __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a,
   static_assert(PPT == 1 || PPT == 2 || PPT == 4, "a round of NSET phases is a whole number of tiles");
   constexpr int ROWB = 4 * CP;           // bytes per split row
   constexpr int NBUF = 3;                // phase buffers in LDS: multiplied | complete, prefetchable | being landed
-  constexpr int NSET = 4;                // register sets of a requesting wave = phases in flight from memory
   constexpr int LEAD = NSET + 2;         // a phase is requested LEAD phases before it is multiplied, landed 2 before
   constexpr int BUFB = TM * 256;         // bytes per phase buffer
-  constexpr int RING = 16;               // tiles in the index / scale rings
-  constexpr int AH_I = 8, AH_S = 4;      // tile t + AH_I's indices and tile t + AH_S's scales are requested at tile t
-  static_assert(RING >= 2 * AH_I && AH_I > LEAD && AH_S >= 3 && AH_S < AH_I, "ring distances");
+  // index / scale pipeline of the requesters: tile t + AH_I's indices and tile t + AH_S's scales are requested at tile t
+  // and published (registers -> LDS ring) DI tiles later, DI tiles = at least NSET phases: vmcnt retires in order, so a
+  // publish that waits for a younger load drains the gathers behind it
+  // (one-phase tiles keep DI = 1: four tiles of registers measured no gain for them inside the benchmark, and the longer
+  // prologue costs their 17-us launches 2 %, profiles/wide_share_ab.json)
+  constexpr int DI = PPT == 1 ? 1 : (NSET + PPT - 1) / PPT;
+  constexpr int AH_S = DI + 2, AH_I = 2 * DI + 3 > DI + (LEAD + PPT - 1) / PPT ? 2 * DI + 3 : DI + (LEAD + PPT - 1) / PPT;
+  constexpr int RING = 32;               // tiles in the index / scale rings
+  // indices: published by tile u - AH_I + DI, read by the scale request (tile u - AH_S) and row_bases (phase u PPT - LEAD);
+  // scales: published by tile u - AH_S + DI <= u - 2, read by the storers at tiles u + 1, u + 2
+  static_assert(AH_I - DI > AH_S && (AH_I - DI) * PPT >= LEAD && AH_S - DI >= 2 && RING >= AH_I + 4, "ring distances");
   // weight ring: k-step g + WD - 1 is requested at step g.  Two steps for the 12-MFMA k-steps of the C_out = 256 shapes
   // (four: same speed in tools/microbench/wide_check, five spilled registers); the C_out <= 128 shapes have six or three
   // MFMAs per k-step -- 200 / 100 cycles, a fraction of an L2 round trip -- so four steps of weights stay in flight
   constexpr int WD = NB >= 2 ? 2 : 4;
-  static_assert(SK % WD == 0, "the weight ring turns a whole number of times per phase (static register indexing)");
+  static_assert(S % WD == 0 && WD - 1 <= S, "the weight ring turns a whole number of times per tile (static register indexing)");
+  // HD > 0: slots of HALF a k-step (one output block, six MFMAs), half-step g + HD - 1 requested at half-step g; the
+  // MFMAs of a k-step then run block by block -- every accumulator still sees its own three terms in the same order
+  static_assert(HD == 0 || (NB == 2 && (2 * S) % HD == 0 && HD >= 2), "half-step weight ring");
   constexpr int LDS_ST = COUT + 4;       // stage row stride (floats)
   constexpr int NSTG = PPT == 1 ? 2 : 1; // one-phase tiles: a tile is staged while the previous one is still going out
   constexpr int HB = PPT / 2;            // phase of the next tile in which rows 32 .. 63 of a finished tile are staged
@@ -187,10 +247,10 @@ __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a,
 #pragma unroll
         for (int jj = 0; jj < NI; ++jj) *reinterpret_cast<f32x4 *>(dst + jj * 1024) = Gs[jj];
       };
-      // index / scale rings: tile u's input rows are loaded at tile u - AH_I and published at tile u - AH_I + 1, its row
-      // scales (through the published indices) loaded at tile u - AH_S and published at u - AH_S + 1 -- a load has a
-      // whole tile to land.  Both requesting waves keep the (identical) rings, so each reads what it wrote itself; the
-      // storing waves see the scales through the phase barriers.
+      // index / scale rings: tile u's input rows are loaded at tile u - AH_I and published at tile u - AH_I + DI, its row
+      // scales (through the published indices) loaded at tile u - AH_S and published at u - AH_S + DI -- DI tiles in
+      // registers, so that a load of a several-phase tile has at least NSET phases to land.  Both requesting waves keep the (identical) rings,
+      // so each reads what it wrote itself; the storing waves see the scales through the phase barriers.
       int *ring_i = reinterpret_cast<int *>(lds + OFF_IDX);
       float *ring_s = reinterpret_cast<float *>(lds + OFF_SC);
       auto load_idx = [&](int i) -> int {   // rows past the tile's end: its last pair again (a valid row)
@@ -198,36 +258,56 @@ __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a,
         return a.pair_in[d.y + min(lane, d.z - 1)];
       };
 #pragma unroll
-      for (int i = 0; i < AH_I - 1; ++i) ring_i[i * TM + lane] = load_idx(i);
+      for (int i = 0; i < AH_I - DI; ++i) ring_i[i * TM + lane] = load_idx(i);
 #pragma unroll
-      for (int i = 0; i < AH_S - 1; ++i) ring_s[i * TM + lane] = a.row_scale[ring_i[i * TM + lane]];
-      int idx_reg = load_idx(AH_I - 1);
-      float sc_reg = a.row_scale[ring_i[(AH_S - 1) * TM + lane]];
-      auto rings = [&](int t) {   // first phase of tile t: publish tile t + AH - 1, request tile t + AH
-        ring_i[((t + AH_I - 1) & (RING - 1)) * TM + lane] = idx_reg;
-        ring_s[((t + AH_S - 1) & (RING - 1)) * TM + lane] = sc_reg;
-        idx_reg = load_idx(t + AH_I);
-        sc_reg = a.row_scale[ring_i[((t + AH_S) & (RING - 1)) * TM + lane]];
+      for (int i = 0; i < AH_S - DI; ++i) ring_s[i * TM + lane] = a.row_scale[ring_i[i * TM + lane]];
+      int idx_reg[DI];
+      float sc_reg[DI];
+#pragma unroll
+      for (int d = 0; d < DI; ++d) idx_reg[d] = load_idx(AH_I - DI + d);
+#pragma unroll
+      for (int d = 0; d < DI; ++d) sc_reg[d] = a.row_scale[ring_i[(AH_S - DI + d) * TM + lane]];
+      // first phase of tile t (register slot d = t % DI): publish tiles t + AH - DI, request tiles t + AH
+      auto rings = [&](int t, int &ir, float &sr) {
+        ring_i[((t + AH_I - DI) & (RING - 1)) * TM + lane] = ir;
+        ring_s[((t + AH_S - DI) & (RING - 1)) * TM + lane] = sr;
+        ir = load_idx(t + AH_I);
+        sr = a.row_scale[ring_i[((t + AH_S) & (RING - 1)) * TM + lane]];
       };
+      DGR_WIDE_CLK(const unsigned long long life0 = DGR_WIDE_NOW(); unsigned long long c_land = 0, c_rings = 0;)
+      unsigned long long c_bar = 0;
       dgr_phase_barrier();   // P0
 #pragma unroll
       for (int j = 0; j < NSET; ++j) request(j, G[j]);
       land(0, G[0]); request(NSET, G[0]);
       land(1, G[1]); request(NSET + 1, G[1]);
       dgr_phase_barrier();   // P1: phases 0 and 1 are in LDS
-      // ---- phase q: land phase q + 2 (requested four phases ago), request phase q + LEAD into the freed set
-      auto phase = [&](int q, f32x4 *Gs) {
-        if (q % PPT == 0) rings(q / PPT);
+      // ---- phase q: land phase q + 2 (requested NSET phases ago), request phase q + LEAD into the freed set
+      auto phase = [&](int q, bool first, f32x4 *Gs, int &ir, float &sr) {   // first: phase 0 of its tile (static)
+        DGR_WIDE_CLK(const unsigned long long t0 = DGR_WIDE_NOW();)
+        if (first) rings(q / PPT, ir, sr);
+        DGR_WIDE_CLK(const unsigned long long t1 = DGR_WIDE_NOW();)
         land(q + 2, Gs);
+        DGR_WIDE_CLK(c_rings += t1 - t0; c_land += DGR_WIDE_NOW() - t1;)
         request(q + LEAD, Gs);
-        dgr_phase_barrier();
+        dgr_wide_barrier(c_bar);
       };
-      for (int q = 0; q < n_loop * PPT; q += NSET) {   // set of phase p = p % NSET: static register indexing
-        phase(q, G[2]);
-        if (q + 1 < n_loop * PPT) phase(q + 1, G[3]);
-        if (q + 2 < n_loop * PPT) phase(q + 2, G[0]);
-        if (q + 3 < n_loop * PPT) phase(q + 3, G[1]);
+      // a round = a whole number of turns of the register sets (phase p in set p % NSET) and of the index / scale
+      // registers (tile t in slot t % DI): static register indexing
+      constexpr int ROUND = dgr_wide_lcm(NSET, PPT * DI);
+      for (int q = 0; q < n_loop * PPT; q += ROUND) {
+#pragma unroll
+        for (int j = 0; j < ROUND; ++j) {
+          if (q + j < n_loop * PPT) phase(q + j, j % PPT == 0, G[(j + 2) % NSET], idx_reg[(j / PPT) % DI], sc_reg[(j / PPT) % DI]);
+        }
       }
+#ifdef DGR_WIDE_STAGE_CLK
+      if (lane == 0) {
+        unsigned long long *c = dgr_wide_stage_clk[dgr_wide_shape_id(CP, NB, WM)];
+        atomicAdd(c + 4, c_bar); atomicAdd(c + 5, c_land); atomicAdd(c + 6, c_rings);
+        atomicAdd(c + 7, DGR_WIDE_NOW() - life0); atomicAdd(c + 8, 1ull);
+      }
+#endif
       return;
     }
     // -------------------------------------------------------------- storers
@@ -253,13 +333,15 @@ __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a,
         if (r < d.z) __builtin_nontemporal_store(v[i], reinterpret_cast<f32x4 *>(a.y + (int64_t)(d.y + r) * COUT + c4));
       }
     };
+    DGR_WIDE_CLK(const unsigned long long life0 = DGR_WIDE_NOW();)
+    unsigned long long c_bar = 0;
     dgr_phase_barrier();   // P0
     dgr_phase_barrier();   // P1
     auto sphase = [&](int t, auto hc) {
       constexpr int h = decltype(hc)::value;
       if constexpr (h == 0) store_rows(t - 2, (PPT - 1) * RPH);
       else store_rows(t - 1, (h - 1) * RPH);
-      dgr_phase_barrier();
+      dgr_wide_barrier(c_bar);
     };
     for (int t = 0; t < n_loop; ++t) {
       sphase(t, std::integral_constant<int, 0>());
@@ -273,22 +355,40 @@ __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a,
       dgr_wait_vmcnt<0>();
       atomicMax(a.clk + 1, (unsigned long long)wall_clock64());
     }
+#ifdef DGR_WIDE_STAGE_CLK
+    if (lane == 0) {
+      unsigned long long *c = dgr_wide_stage_clk[dgr_wide_shape_id(CP, NB, WM)];
+      atomicAdd(c + 9, c_bar); atomicAdd(c + 10, DGR_WIDE_NOW() - life0); atomicAdd(c + 11, 1ull);
+    }
+#endif
     return;
   }
 
   // ================================================================== compute waves
   const int wn = wave % WN, wm = wave / WN;   // output-channel block / row half of this wave
   int4 dc = desc(0), dn = desc(1);   // this tile's and the next tile's descriptor
-  uint4 w[WD][NB][NP];
-  auto wload = [&](int k, int s, uint4 (*ws)[NP]) {
-    const uint4 *p = a.wb + ((int64_t)(k * S + s) * NBLK + wn * NB) * 64 + lane;
+  // ring slots of one output block (both pieces): whole k-steps -- block j of step g in slot (g % WD) NB + j; half steps
+  // -- half-step 2 g + j in slot (2 g + j) % HD
+  constexpr int NW = HD > 0 ? HD : WD * NB;
+  uint4 w[NW][NP];
+  auto wload1 = [&](int k, int s, int j, uint4 *ws) {
+    const uint4 *p = a.wb + ((int64_t)(k * S + s) * NBLK + wn * NB + j) * 64 + lane;
 #pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-      for (int pc = 0; pc < NP; ++pc) ws[j][pc] = p[(int64_t)pc * a.piece_stride + j * 64];
+    for (int pc = 0; pc < NP; ++pc) ws[pc] = p[(int64_t)pc * a.piece_stride];
   };
+  auto wload = [&](int k, int s, uint4 (*ws)[NP]) {
 #pragma unroll
-  for (int g = 0; g < WD - 1; ++g) wload(dc.x, g % S, w[g]);
+    for (int j = 0; j < NB; ++j) wload1(k, s, j, ws[j]);
+  };
+  if constexpr (HD > 0) {
+#pragma unroll
+    for (int g = 0; g < HD - 1; ++g) wload1(dc.x, (g / 2) % S, g % 2, w[g]);
+  } else {
+#pragma unroll
+    for (int g = 0; g < WD - 1; ++g) wload(dc.x, g % S, &w[g * NB]);
+  }
+  DGR_WIDE_CLK(const unsigned long long life0 = DGR_WIDE_NOW(), wall0 = wall_clock64(); unsigned long long c_w = 0;)
+  unsigned long long c_bar = 0;
   dgr_phase_barrier();   // P0
   dgr_phase_barrier();   // P1
   // operands of k-step s out of phase buffer b: row = 32 (MB wm + i) + (lane & 31), chunk = 2 s + (lane >> 5) of piece h
@@ -297,15 +397,17 @@ __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a,
   // byte offset of this lane's h chunk of k-step 0 in its first row; k-step s: ^ (32 s) (chunk 2 s + (lane >> 5) =
   // 2 s ^ (lane >> 5)); the m chunk: ^ 128.  (The row term is a multiple of 256: it does not meet the xor bits.)
   const int lofs0 = (32 * MB * wm + (lane & 31)) * 256 + 16 * ((lane >> 5) ^ (lane & 15));
-  auto oload = [&](int b, int s, uint4 (*o)[NP]) {
+  constexpr bool XM1 = HD >= 8;
+  auto oload_part = [&](int b, int s, uint4 (*o)[NP], bool xh, bool xm) {
     const unsigned char *p = lds + b * BUFB + (lofs0 ^ (32 * s));
     const unsigned char *pm = lds + b * BUFB + (lofs0 ^ (32 * s) ^ 128);
 #pragma unroll
     for (int i = 0; i < MB; ++i) {
-      o[i][0] = *reinterpret_cast<const uint4 *>(p + i * 32 * 256);
-      o[i][1] = *reinterpret_cast<const uint4 *>(pm + i * 32 * 256);
+      if (xh) o[i][0] = *reinterpret_cast<const uint4 *>(p + i * 32 * 256);
+      if (xm) o[i][1] = *reinterpret_cast<const uint4 *>(pm + i * 32 * 256);
     }
   };
+  auto oload = [&](int b, int s, uint4 (*o)[NP]) { oload_part(b, s, o, true, true); };
   oload(0, 0, op[0]);
   int buf = 0;
   // raw accumulators of this wave's row group i -> LDS stage, NPC 16-byte pieces per k-step (of the group's 4 NB):
@@ -342,26 +444,65 @@ __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a,
       const int s0 = h * SK;
 #pragma unroll
       for (int s = 0; s < SK; ++s) {
-        {   // unconditional (past the last tile: the last tile's descriptor again), so the wait counts are static
-          const int sg = s0 + s + WD - 1;
-          wload(sg < S ? dc.x : dn.x, sg < S ? sg : sg - S, w[(s + WD - 1) % WD]);
-        }
-        // next k-step's operands; the next phase's buffer has been complete since the last barrier
-        if (s + 1 < SK) oload(buf, s + 1, op[(s + 1) & 1]);
-        else oload(nbuf, 0, op[0]);
-        // pin the prefetches ahead of the MFMA block (left to the compiler, or interleaved one per MFMA gap with
-        // sched_group_barrier, the loads are waited for early: 2.36 / 2.19 ms against 1.95 ms, tools/microbench/wide_check)
-        __builtin_amdgcn_sched_barrier(0);
-        uint4 (*wc)[NP] = w[s % WD];
         uint4 (*oc)[NP] = op[s & 1];
-#define DGR_WIDE_TERM(WP, OP)                                                                                         \
-  _Pragma("unroll") for (int i = 0; i < MB; ++i) _Pragma("unroll") for (int j = 0; j < NB; ++j)                       \
-      ac[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wc[j][WP]),                          \
-                                                        __builtin_bit_cast(f16x8, oc[i][OP]), ac[i][j], 0, 0, 0);
-        DGR_WIDE_TERM(1, 0)   // wm . xh
-        DGR_WIDE_TERM(0, 1)   // wh . xm
-        DGR_WIDE_TERM(0, 0)   // wh . xh
+        // instrumented build: the time from "requests issued" to "this step's fragments are in their registers"
+#define DGR_WIDE_WEIGHT_WAIT(W0, W1)                                                                                  \
+  DGR_WIDE_CLK(__builtin_amdgcn_sched_barrier(0);                                                                     \
+               asm volatile("" ::"v"(__builtin_bit_cast(f16x8, (W0)[0])), "v"(__builtin_bit_cast(f16x8, (W0)[1])),     \
+                            "v"(__builtin_bit_cast(f16x8, (W1)[0])), "v"(__builtin_bit_cast(f16x8, (W1)[1])));         \
+               const unsigned long long tw1 = DGR_WIDE_NOW(); __builtin_amdgcn_sched_barrier(0);)
+#define DGR_WIDE_TERM(WP, OX, J0, J1, WJ)                                                                             \
+  _Pragma("unroll") for (int i = 0; i < MB; ++i) _Pragma("unroll") for (int j = J0; j < J1; ++j)                      \
+      ac[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, (WJ)[WP]),                           \
+                                                        __builtin_bit_cast(f16x8, OX), ac[i][j], 0, 0, 0);
+        if constexpr (HD == 0) {
+          {   // unconditional (past the last tile: the last tile's descriptor again), so the wait counts are static
+            const int sg = s0 + s + WD - 1;
+            wload(sg < S ? dc.x : dn.x, sg < S ? sg : sg - S, &w[(sg % WD) * NB]);
+          }
+          DGR_WIDE_CLK(const unsigned long long tw0 = DGR_WIDE_NOW();)
+          // next k-step's operands; the next phase's buffer has been complete since the last barrier
+          if (s + 1 < SK) oload(buf, s + 1, op[(s + 1) & 1]);
+          else oload(nbuf, 0, op[0]);
+          // pin the prefetches ahead of the MFMA block (left to the compiler, or interleaved one per MFMA gap with
+          // sched_group_barrier, the loads are waited for early: 2.36 / 2.19 ms against 1.95 ms, tools/microbench/wide_check)
+          __builtin_amdgcn_sched_barrier(0);
+          uint4 (*wc)[NP] = &w[((s0 + s) % WD) * NB];
+          DGR_WIDE_WEIGHT_WAIT(wc[0], wc[NB - 1])
+          DGR_WIDE_TERM(1, oc[i][0], 0, NB, wc[j])   // wm . xh
+          DGR_WIDE_TERM(0, oc[i][1], 0, NB, wc[j])   // wh . xm
+          DGR_WIDE_TERM(0, oc[i][0], 0, NB, wc[j])   // wh . xh
+          DGR_WIDE_CLK(__builtin_amdgcn_sched_barrier(0); c_w += tw1 - tw0;)
+        } else {
+#pragma unroll
+          for (int jb = 0; jb < 2; ++jb) {   // half-step g = 2 (s0 + s) + jb of the tile: output block jb
+            constexpr int G2 = 2 * S;
+            const int g = 2 * (s0 + s) + jb, gg = g + HD - 1;
+            wload1(gg < G2 ? dc.x : dn.x, (gg % G2) / 2, gg % 2, w[gg % HD]);
+            DGR_WIDE_CLK(const unsigned long long tw0 = DGR_WIDE_NOW();)
+            // XM1: the m planes are single-buffered (op[0][.][1]): the next k-step's are requested after their last
+            // use, the wh . xm term of block 1 -- eight registers for the ring
+            if (jb == 0) {
+              if (s + 1 < SK) oload_part(buf, s + 1, op[(s + 1) & 1], true, !XM1);
+              else oload_part(nbuf, 0, op[0], true, !XM1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            uint4 *wc = w[g % HD];
+            DGR_WIDE_WEIGHT_WAIT(wc, wc)
+            DGR_WIDE_TERM(1, oc[i][0], jb, jb + 1, wc)
+            DGR_WIDE_TERM(0, op[XM1 ? 0 : s & 1][i][1], jb, jb + 1, wc)
+            if (XM1 && jb == 1) {
+              __builtin_amdgcn_sched_barrier(0);
+              if (s + 1 < SK) oload_part(buf, s + 1, op[0], false, true);
+              else oload_part(nbuf, 0, op[0], false, true);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+            DGR_WIDE_TERM(0, oc[i][0], jb, jb + 1, wc)
+            DGR_WIDE_CLK(__builtin_amdgcn_sched_barrier(0); c_w += tw1 - tw0;)
+          }
+        }
 #undef DGR_WIDE_TERM
+#undef DGR_WIDE_WEIGHT_WAIT
         // the finished tile's accumulators leave for the stage a few pieces per k-step, in the shadow of the MFMAs
         // (MB = 2: row group 0 in phase 0, row group 1 in phase HB; MB = 1: the wave's one row group in phase 0)
         if (stage_prev) {
@@ -376,7 +517,7 @@ __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a,
         dn = desc(t + 2);
       }
       buf = nbuf;
-      dgr_phase_barrier();
+      dgr_wide_barrier(c_bar);
     }
   };
   f32x16 accA[MB][NB], accB[MB][NB];
@@ -385,15 +526,26 @@ __global__ void __launch_bounds__(512, 1) sparse_conv_wide_f16x2(ConvWideArgs a,
     if (t + 1 < n_loop) ctile(t + 1, accB, accA);
   }
   if (a.clk && lane == 0) atomicMax(a.clk + 1, (unsigned long long)wall_clock64());
+#ifdef DGR_WIDE_STAGE_CLK
+  if (lane == 0) {
+    unsigned long long *c = dgr_wide_stage_clk[dgr_wide_shape_id(CP, NB, WM)];
+    const unsigned long long life = DGR_WIDE_NOW() - life0;
+    atomicAdd(c + 0, c_bar); atomicAdd(c + 1, c_w); atomicAdd(c + 2, life); atomicAdd(c + 3, 1ull);
+    if (wave == 0) {
+      atomicAdd(c + 12, (unsigned long long)(n_loop * PPT)); atomicAdd(c + 13, life);
+      atomicAdd(c + 14, (unsigned long long)wall_clock64() - wall0);
+    }
+  }
+#endif
 }
 
-template <int CP, int NB, int WM>
+template <int CP, int NB, int WM, int NSET, int HD>
 static int launch_wide(const ConvWideArgs &ka, const int4 *tile_desc, int64_t tile_bound, int num_cus, hipStream_t stream) {
   int64_t grid = num_cus;
   if (tile_bound < grid) grid = tile_bound;
   grid = (grid + 7) / 8 * 8;
   if (grid < 8) grid = 8;
-  sparse_conv_wide_f16x2<CP, NB, WM><<<(int)grid, 512, 0, stream>>>(ka, tile_desc);
+  sparse_conv_wide_f16x2<CP, NB, WM, NSET, HD><<<(int)grid, 512, 0, stream>>>(ka, tile_desc);
   DGR_LAUNCH_CHECK();
   return DGR_OK;
 }
@@ -419,8 +571,11 @@ int dgr_conv_wide_launch(const DgrConvLaunch &a, const DgrSplitRows &in, const v
 #define DGR_WIDE(CPV, NBV, WMV)                                                                 \
   do {                                                                                          \
     if (kernel_name) *kernel_name = "sparse_conv_wide_f16x2<" #CPV ", " #NBV ", " #WMV ">";     \
-    return launch_wide<CPV, NBV, WMV>(ka, a.tile_desc, tile_bound, num_cus, stream);            \
+    return launch_wide<CPV, NBV, WMV, 4, (NBV == 2 ? 8 : 0)>(ka, a.tile_desc, tile_bound, num_cus, stream); \
   } while (0)
+  // One variant per shape for every num_cus: four gather sets (six were slower inside the benchmark) and, for the
+  // C_out = 256 shapes, the weight ring of eight half steps, which wins on a 64-CU share and on the whole GPU alike
+  // (profiles/wide_share_ab.json)
   if (a.cout == 64 && a.cin == 64) DGR_WIDE(64, 1, 2);
   if (a.cout == 128 && a.cin == 64) DGR_WIDE(64, 1, 1);
   if (a.cout == 128 && a.cin == 128) DGR_WIDE(128, 1, 1);

@@ -1136,26 +1136,28 @@ extern "C" int dgr_net_rerun_layer(dgr_ctx *ctx, dgr_net *net, int layer, int re
               "the kernel maps of the last forward are gone: a later call on this context reused its workspace");
   DGR_REQUIRE(!r.fused_pairs, "layer %d ran fused with its neighbour search; not re-runnable", layer);
   const DgrLayer &L = net->W->layers[layer];
+  // on the context's CU-masked stream if it has one (ctx->num_cus is then the share's size), else on the null stream
+  hipStream_t st = ctx->part_stream;
   hipEvent_t e0, e1, e2;
   DGR_HIP_CHECK(hipEventCreate(&e0)); DGR_HIP_CHECK(hipEventCreate(&e1)); DGR_HIP_CHECK(hipEventCreate(&e2));
   float tg = 0.f, tr = 0.f;
   for (int i = 0; i < reps + 1; ++i) {  // first iteration = warm-up
-    DGR_HIP_CHECK(hipEventRecord(e0, nullptr));
+    DGR_HIP_CHECK(hipEventRecord(e0, st));
     if (r.os)
-      DGR_CHECK(dgr_conv_os_launch(r.os_launch, nullptr));
+      DGR_CHECK(dgr_conv_os_launch(r.os_launch, st));
     else if (r.small_cin)
       DGR_CHECK(dgr_conv_small_cin(r.launch.in, r.launch.in_ld, r.launch.in_relu, L.cin, L.w, L.wq, L.shift, r.km, r.n_out,
-                                   r.n_out_cap, r.launch.out, r.launch.out_ld, nullptr));
+                                   r.n_out_cap, r.launch.out, r.launch.out_ld, st));
     else if (L.wb && r.has_reduce)
-      DGR_CHECK(dgr_conv_wide_launch(r.launch, r.split_in, L.wb, L.wb_piece, L.w_unscale, ctx->num_cus, nullptr));
+      DGR_CHECK(dgr_conv_wide_launch(r.launch, r.split_in, L.wb, L.wb_piece, L.w_unscale, ctx->num_cus, st));
     else
-      DGR_CHECK(dgr_conv_launch(r.launch, ctx->num_cus, nullptr));
-    DGR_HIP_CHECK(hipEventRecord(e1, nullptr));
+      DGR_CHECK(dgr_conv_launch(r.launch, ctx->num_cus, st));
+    DGR_HIP_CHECK(hipEventRecord(e1, st));
     if (r.has_reduce && !r.small_cin && !r.os)
       DGR_CHECK(dgr_reduce_rows(r.launch.y, L.cout, r.red_ptr, r.red_pos, r.n_out, r.n_out_cap,
-                                r.split_only ? nullptr : r.launch.out, r.launch.out_ld, L.shift, r.res, r.res_ld, r.res_relu, nullptr,
+                                r.split_only ? nullptr : r.launch.out, r.launch.out_ld, L.shift, r.res, r.res_ld, r.res_relu, st,
                                 r.split_out.planes ? &r.split_out : nullptr, r.out_relu));
-    DGR_HIP_CHECK(hipEventRecord(e2, nullptr));
+    DGR_HIP_CHECK(hipEventRecord(e2, st));
     DGR_HIP_CHECK(hipEventSynchronize(e2));
     float a = 0.f, b = 0.f;
     DGR_HIP_CHECK(hipEventElapsedTime(&a, e0, e1));

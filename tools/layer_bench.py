@@ -3,11 +3,13 @@
 the 6-D inlier net and of the 3-D FCGF net prints pairs, shape, GFLOP, MFMA-phase and reduce-phase
 time, TFLOP/s and the implied GB/s of the gather + product-row traffic.  Kernel-tuning instrument.
 
-    python tools/layer_bench.py [LAYERS|all] [RERUNS]
+    python tools/layer_bench.py [LAYERS|all] [RERUNS] [SHARES]
 
 LAYERS: comma-separated layer numbers; RERUNS > 0: after the warm-up rerun of five, time every layer RERUNS times one by
-one and print the median (min-max) and the sorted samples of the MFMA-phase time (the A/B records of profiles/)."""
-import os, statistics, sys
+one and print the median (min-max) and the sorted samples of the MFMA-phase time (the A/B records of profiles/);
+SHARES = 2 or 4: everything runs on share 0 of that many equal shares of the compute units (ops.partition_stream), the
+state in which one context of the timed benchmark configuration runs its kernels."""
+import contextlib, os, statistics, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepglobalregistration_amd import ops, synth
@@ -15,6 +17,10 @@ from deepglobalregistration_amd.core.deep_global_registration import DeepGlobalR
 
 layers = [int(x) for x in sys.argv[1].split(',')] if len(sys.argv) > 1 and sys.argv[1] != 'all' else None
 reruns = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+shares = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+share = ops.partition_stream('cuda', 0, shares)
+stack = contextlib.ExitStack()
+stack.enter_context(torch.cuda.stream(share) if share is not None else contextlib.nullcontext())
 ck = synth.synth_checkpoint(0)
 dgr = DeepGlobalRegistration({'weights': ck}, torch.device('cuda'))
 x0, x1, T = synth.synth_pair(0, 50000)
