@@ -57,6 +57,7 @@ SIGNATURES = {
     'dgr_net_param_bytes': (C.c_int64, [vp]),
     'dgr_net_share': (C.c_int, [vp, vp, C.POINTER(vp)]),
     'dgr_net_sharers': (C.c_int, [vp]),
+    'dgr_net_set_wide_coarse': (C.c_int, [vp, C.c_int]),
     'dgr_resunet_forward': (C.c_int, [vp, vp, vp, vp, C.c_int64, vp, vp]),
     'dgr_net_get_intermediate': (C.c_int, [vp, vp, C.c_char_p, vp, C.c_int64, c_i64p, c_i64p]),
     'dgr_net_get_tensor': (C.c_int, [vp, vp, C.c_char_p, C.c_int, vp, C.c_int64, c_i64p, c_i64p]),

@@ -169,7 +169,7 @@ struct DgrMapSet {
 // Builds all coordinate maps and kernel maps of one sparse tensor into `arena`.
 int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int conv1_ks,
                    DgrMapSet *ms, hipStream_t stream, bool skip_conv1_map = false, bool lean = false,
-                   bool nbr_tables = false);
+                   bool nbr_tables = false, bool nbr_lists = false);
 // per-offset pair counts of a neighbour table (statistics / tests; synchronises)
 int dgr_nbr_counts(const DgrNbrTable &t, const int32_t *n_out_dev, int64_t counts[27]);
 // conv1 fused with its neighbour search (D = 3, Cin <= 8, Cout = 32): no kernel map for the ks^3 offsets

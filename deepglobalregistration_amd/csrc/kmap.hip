@@ -946,12 +946,140 @@ int dgr_nbr_counts(const DgrNbrTable &t, const int32_t *n_out_dev, int64_t count
   return DGR_OK;
 }
 
+// ---- D = 3: rule-major lists FROM a neighbour table, for the layers of the 3-D net that run on the wide rule-major
+// kernel (conv_wide.hip + dgr_reduce_rows): rule k = the rows o with nbr[k][o] >= 0 in ascending o, a row's out_pos
+// entries = its valid offsets in ascending k -- the contract of a lean rule-major map without a second
+// hash search.  Counting per (offset, 256-row block) and per row, ONE multi-array scan, one fill; the maps of a forward
+// go through each launch together (blockIdx.y = map).  No atomics: every position is a prefix sum, two builds are equal.
+constexpr int NL_JOBS = 3;
+struct NbrListJobs {
+  const int32_t *nbr[NL_JOBS], *n_out_dev[NL_JOBS];
+  long long n_pad[NL_JOBS], n_cap[NL_JOBS];
+  int RB[NL_JOBS];                                       // 256-row blocks covering rows 0 .. n_cap (out_ptr has n_cap + 1 entries)
+  int32_t *counts[NL_JOBS], *cnt_out[NL_JOBS];           // pass 1: pairs per (offset, block) [27 * RB] and per row [n_cap + 1]
+  const int32_t *base[NL_JOBS], *out_ptr[NL_JOBS];       // ... scanned
+  int32_t *pair_in[NL_JOBS], *out_pos[NL_JOBS];
+};
+__global__ void __launch_bounds__(KM_THREADS) nbr_list_count(NbrListJobs J) {
+  __shared__ int wcnt[KM_THREADS / 64][27];
+  const int m = blockIdx.y, b = blockIdx.x;
+  if (b >= J.RB[m]) return;
+  const int64_t o = (int64_t)b * KM_THREADS + threadIdx.x, n_pad = J.n_pad[m];
+  const int32_t *__restrict__ nbr = J.nbr[m];
+  const bool live = o < *J.n_out_dev[m];   // (n_out <= n_cap <= n_pad: a live row lies inside the table)
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < 27; ++k) {
+    const bool hit = live && nbr[(int64_t)k * n_pad + o] >= 0;
+    mine += hit;
+    const unsigned long long bal = __ballot(hit);
+    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6][k] = __popcll(bal);
+  }
+  __syncthreads();
+  if (threadIdx.x < 27) {
+    int n = 0;
+    for (int w = 0; w < KM_THREADS / 64; ++w) n += wcnt[w][threadIdx.x];
+    J.counts[m][(int64_t)threadIdx.x * J.RB[m] + b] = n;
+  }
+  if (o <= J.n_cap[m]) J.cnt_out[m][o] = mine;
+}
+__global__ void __launch_bounds__(KM_THREADS) nbr_list_fill(NbrListJobs J) {
+  __shared__ int wcnt[KM_THREADS / 64][27];
+  const int m = blockIdx.y, b = blockIdx.x;
+  if (b >= J.RB[m]) return;
+  const int64_t o = (int64_t)b * KM_THREADS + threadIdx.x, n_pad = J.n_pad[m];
+  const int32_t *__restrict__ nbr = J.nbr[m];
+  if ((int64_t)b * KM_THREADS >= *J.n_out_dev[m]) return;   // (the whole block: no barrier is skipped by a part of it)
+  const bool live = o < *J.n_out_dev[m];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 27; ++k) {
+    const unsigned long long bal = __ballot(live && nbr[(int64_t)k * n_pad + o] >= 0);
+    if (lane == 0) wcnt[wave][k] = __popcll(bal);
+  }
+  __syncthreads();
+  int slot = live ? J.out_ptr[m][o] : 0;
+  int32_t *__restrict__ pair_in = J.pair_in[m], *__restrict__ out_pos = J.out_pos[m];
+#pragma unroll
+  for (int k = 0; k < 27; ++k) {
+    const int v = live ? nbr[(int64_t)k * n_pad + o] : -1;
+    const unsigned long long bal = __ballot(v >= 0);
+    if (v < 0) continue;
+    int pos = J.base[m][(int64_t)k * J.RB[m] + b] + __popcll(bal & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) pos += wcnt[w][k];
+    pair_in[pos] = v;        // pos < 27 n_cap = pair_cap: at most one pair per (offset, row)
+    out_pos[slot++] = pos;   // the row's slots [out_ptr[o], out_ptr[o + 1]) in ascending k
+  }
+}
+
+// Lists for `nj` tables (in, out level, table, map); the scanned temporaries are released before returning.
+struct NbrListSpec {
+  const DgrNbrTable *t;
+  const DgrCoordMap *out;
+  DgrKernelMap *km;
+};
+static int build_nbr_lists3(DgrArena &arena, const NbrListSpec *specs, int nj, hipStream_t stream) {
+  DGR_REQUIRE(nj >= 1 && nj <= NL_JOBS && 2 * nj <= DGR_SCAN_MAX, "neighbour-table lists: %d maps per call", nj);
+  NbrListJobs J = {};
+  FinalizeJobs fj = {};
+  for (int m = 0; m < nj; ++m) {
+    DgrKernelMap *km = specs[m].km;
+    const int64_t n_cap = specs[m].out->n_cap;
+    DGR_REQUIRE(specs[m].t->built && specs[m].t->n_pad >= n_cap, "neighbour-table lists: table %d is not built", m);
+    km->K = 27;
+    km->pair_cap = 27 * n_cap;
+    DGR_REQUIRE(km->pair_cap < (1ll << 31), "kernel map too large (%lld pairs)", (long long)km->pair_cap);
+    km->tile_cap = km->pair_cap / DGR_TILE_M + 27;
+    DGR_ALLOC(km->rule_ptr, arena, int32_t, 28);
+    DGR_ALLOC(km->tile_ptr, arena, int32_t, 28);
+    DGR_ALLOC(km->pair_in, arena, int32_t, km->pair_cap);
+    DGR_ALLOC(km->tile_desc, arena, int4, km->tile_cap);
+    DGR_ALLOC(km->out_ptr, arena, int32_t, n_cap + 1);
+    DGR_ALLOC(km->out_pos, arena, int32_t, km->pair_cap);
+    km->pair_out = nullptr; km->pair_k = nullptr; km->in_ptr = km->in_pos = nullptr;
+  }
+  DgrArena::Mark mk = arena.mark();
+  const int32_t *ins[2 * NL_JOBS];
+  int32_t *outs[2 * NL_JOBS], *tots[2 * NL_JOBS];
+  int64_t ns[2 * NL_JOBS];
+  int max_rb = 0;
+  long long max_tiles = 0;
+  for (int m = 0; m < nj; ++m) {
+    DgrKernelMap *km = specs[m].km;
+    const int64_t n_cap = specs[m].out->n_cap;
+    const int RB = (int)dgr_ceil_div(n_cap + 1, KM_THREADS);
+    int32_t *counts, *base, *total, *cnt_out;
+    DGR_ALLOC(counts, arena, int32_t, (int64_t)27 * RB);
+    DGR_ALLOC(base, arena, int32_t, (int64_t)27 * RB);
+    DGR_ALLOC(total, arena, int32_t, 1);
+    DGR_ALLOC(cnt_out, arena, int32_t, n_cap + 1);
+    J.nbr[m] = specs[m].t->nbr; J.n_out_dev[m] = specs[m].out->n_dev; J.n_pad[m] = specs[m].t->n_pad; J.n_cap[m] = n_cap;
+    J.RB[m] = RB; J.counts[m] = counts; J.cnt_out[m] = cnt_out; J.base[m] = base; J.out_ptr[m] = km->out_ptr;
+    J.pair_in[m] = km->pair_in; J.out_pos[m] = km->out_pos;
+    ins[2 * m] = cnt_out; outs[2 * m] = km->out_ptr; tots[2 * m] = nullptr; ns[2 * m] = n_cap + 1;
+    ins[2 * m + 1] = counts; outs[2 * m + 1] = base; tots[2 * m + 1] = total; ns[2 * m + 1] = (int64_t)27 * RB;
+    finalize_job(fj, m, base, total, 27, RB, km);
+    max_rb = std::max(max_rb, RB);
+    max_tiles = std::max<long long>(max_tiles, km->tile_cap);
+  }
+  nbr_list_count<<<dim3((unsigned)max_rb, (unsigned)nj), KM_THREADS, 0, stream>>>(J);
+  DGR_LAUNCH_CHECK();
+  DGR_CHECK(dgr_exclusive_scan_multi(arena, 2 * nj, ins, outs, ns, tots, stream));
+  kmap_finalize<<<nj, 1024, 0, stream>>>(fj);
+  tile_desc_kernel<<<dim3((unsigned)dgr_ceil_div(max_tiles, 256), (unsigned)nj), 256, 0, stream>>>(fj);
+  nbr_list_fill<<<dim3((unsigned)max_rb, (unsigned)nj), KM_THREADS, 0, stream>>>(J);
+  DGR_LAUNCH_CHECK();
+  arena.rewind(mk);
+  for (int m = 0; m < nj; ++m) specs[m].km->built = true;
+  return DGR_OK;
+}
+
 int dgr_build_coord_maps(DgrArena &arena, const int32_t *coords, int64_t N, DgrMapSet *ms,
                          hipStream_t stream);
 int dgr_build_half_buckets(DgrArena &arena, DgrCoordMap *cm, DgrHalfBuckets *hb, int levels, int renumber_from, hipStream_t stream);
 
 int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int conv1_ks,
-                   DgrMapSet *ms, hipStream_t stream, bool skip_conv1_map, bool lean, bool nbr_tables) {
+                   DgrMapSet *ms, hipStream_t stream, bool skip_conv1_map, bool lean, bool nbr_tables, bool nbr_lists) {
   DGR_REQUIRE(D == 3 || D == 6, "D=%d not supported (the DGR path uses D=3 and D=6)", D);
   DGR_REQUIRE(conv1_ks % 2 == 1 && conv1_ks >= 1, "conv1 kernel size must be odd");
   DGR_REQUIRE(N > 0 && N < (1ll << 30), "N=%lld out of range", (long long)N);
@@ -990,6 +1118,13 @@ int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int
       cls_count_kernel<<<dim3((unsigned)max_nb, 3), KM_THREADS, 0, stream>>>(cj);
       cls_fill_kernel<<<dim3((unsigned)max_nb, 3), KM_THREADS, 0, stream>>>(cj);
       DGR_LAUNCH_CHECK();
+    }
+    if (lean && nbr_lists) {
+      // ... plus rule-major lists of the two coarse same-stride tables and the level 2 -> 3 strided one: the 128 / 256-channel
+      // layers there run on the wide rule-major kernel (net.hip, Fwd::conv)
+      const NbrListSpec specs[3] = {{&ms->nsame[2], &ms->cm[2], &ms->same[2]}, {&ms->nsame[3], &ms->cm[3], &ms->same[3]},
+                                    {&ms->ndown[2], &ms->cm[3], &ms->down[2]}};
+      DGR_CHECK(build_nbr_lists3(arena, specs, 3, stream));
     }
     if (lean) {   // the network forward needs nothing else (conv1 runs fused with its neighbour search)
       if (conv1_ks != 3 && !skip_conv1_map)
@@ -1044,7 +1179,9 @@ struct dgr_maps {
 static int maps_create(dgr_ctx *ctx, const int32_t *coords, int64_t N, int D, int conv1_kernel_size, int flags,
                        dgr_maps **out, dgr_stream stream_) {
   DGR_REQUIRE(ctx && coords && out, "dgr_maps_create: NULL argument");
-  DGR_REQUIRE((flags & ~DGR_MAPS_LEAN) == 0, "dgr_maps_create_ex: unknown flags 0x%x", flags);
+  DGR_REQUIRE((flags & ~(DGR_MAPS_LEAN | DGR_MAPS_NBR_LISTS)) == 0, "dgr_maps_create_ex: unknown flags 0x%x", flags);
+  DGR_REQUIRE(!(flags & DGR_MAPS_NBR_LISTS) || ((flags & DGR_MAPS_LEAN) && D == 3),
+              "dgr_maps_create_ex: DGR_MAPS_NBR_LISTS goes with DGR_MAPS_LEAN and D = 3");
   // lean: the arguments of dgr_resunet_forward_impl (net.hip) -- a 3-D net runs on neighbour tables with conv1 fused
   // with its search (no conv1 map), a 6-D net on lean rule-major maps
   const bool lean = (flags & DGR_MAPS_LEAN) != 0;
@@ -1060,7 +1197,8 @@ static int maps_create(dgr_ctx *ctx, const int32_t *coords, int64_t N, int D, in
     if (!m->coords_copy) { rc = DGR_ENOMEM; break; }
     if (hipMemcpyAsync(m->coords_copy, coords, (size_t)N * (D + 1) * sizeof(int32_t),
                        hipMemcpyDeviceToDevice, stream) != hipSuccess) { rc = DGR_EHIP; break; }
-    rc = dgr_build_maps(m->arena, m->coords_copy, N, D, conv1_kernel_size, &m->ms, stream, skip_conv1_map, lean, D == 3);
+    rc = dgr_build_maps(m->arena, m->coords_copy, N, D, conv1_kernel_size, &m->ms, stream, skip_conv1_map, lean, D == 3,
+                        (flags & DGR_MAPS_NBR_LISTS) != 0);
     if (rc != DGR_OK) break;
     int32_t flag = 0;
     if (hipMemcpyAsync(&flag, m->ms.overflow, sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||

@@ -114,6 +114,9 @@ struct dgr_net {
   std::map<std::string, DgrTensorRef> inter;
   std::map<std::string, DgrTensorRec> tensors;
   uint64_t run_generation = 0;   // arena generation `runs` / `inter` point into
+  // 3-D net on neighbour tables: the 128 / 256-channel layers of the two coarse levels run on the wide rule-major kernel
+  // (dgr_net_set_wide_coarse; off: every K = 27 layer output-stationary, with row maxima behind every tensor)
+  bool wide_coarse = false;
 };
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -259,7 +262,13 @@ static int make_layer(dgr_net *net, WeightPrep &P, const dgr_weight_desc *descs,
   const float w_scale = ldexpf(1.f, 15 - ex);
   L.w_unscale = ldexpf(1.f, ex - 15);
   const bool use_wide = K > 1 && !dgr_exact_f32() && dgr_conv_wide_supported(L.cin_pad, cin, cout) && !(net->D == 3 && K == 27);
-  if (use_wide) {
+  // 3-D nets that run on neighbour tables: the same-stride and strided (not the transposed) 128 / 256-channel layers of
+  // the two coarse levels ALSO get the wide kernel's operands -- they run on it over lists derived from the tables
+  // (Fwd::conv), next to the w16 / w16b copies of the output-stationary kernel, which DGR_NO_WIDE3=1 still selects
+  const bool transposed = name.size() > 3 && name.compare(name.size() - 3, 3, "_tr") == 0;
+  const bool wide3 = net->D == 3 && K == 27 && net->cin <= 8 && net->conv1_ks <= 7 && !transposed && !dgr_exact_f32() &&
+                     cin >= 128 && cout >= 128 && dgr_conv_wide_supported(L.cin_pad, cin, cout);
+  if (use_wide || wide3) {
     const int S16 = cin / 16, NB32 = cout / 32;
     L.wb_piece = (int64_t)K * S16 * NB32 * 64;
     const int64_t ne = L.wb_piece * 8;
@@ -276,7 +285,8 @@ static int make_layer(dgr_net *net, WeightPrep &P, const dgr_weight_desc *descs,
       dst[ne + o] = dgr_f16_bits_dev(xs - dgr_f16_val_dev(xs));
     }));
     W.param_bytes += (size_t)2 * ne * sizeof(uint16_t);
-  } else {
+  }
+  if (!use_wide) {
     const int S = L.cin_pad / 8, NBLK = L.cout_pad / 32;
     const int64_t ne = (int64_t)K * S * NBLK * 256;
     DGR_CHECK(W.alloc(&L.w, ne));
@@ -460,7 +470,15 @@ extern "C" int dgr_net_share(dgr_ctx *ctx, const dgr_net *src, dgr_net **out) {
   net->D = src->D; net->cin = src->cin; net->cout = src->cout;
   net->conv1_ks = src->conv1_ks; net->normalize = src->normalize;
   net->W = src->W;
+  net->wide_coarse = src->wide_coarse;
   *out = net;
+  return DGR_OK;
+}
+
+extern "C" int dgr_net_set_wide_coarse(dgr_net *net, int on) {
+  DGR_REQUIRE(net, "dgr_net_set_wide_coarse: NULL argument");
+  DGR_REQUIRE(net->D == 3 || !on, "dgr_net_set_wide_coarse: a D = 3 option (the 6-D net runs its wide layers rule-major anyway)");
+  net->wide_coarse = on != 0;
   return DGR_OK;
 }
 
@@ -486,6 +504,10 @@ struct Tensor {
   // tensor) -- they are not written and `dsplit` is the tensor's own buffer
   unsigned char *dsplit = nullptr;
   bool dsplit_only = false;
+  // 3-D net, tensors between the output-stationary kernels and the wide rule-major layers of the coarse levels: the
+  // producer could not leave the representation the consumer reads, so the consumer's launch makes it first --
+  // split_pending: `split` from the f32 rows (dgr_split_rows); amax_pending: `amax` from the f32 rows (dgr_row_amax)
+  bool split_pending = false, amax_pending = false;
 };
 
 struct Fwd {
@@ -495,6 +517,7 @@ struct Fwd {
   DgrMapSet ms;
   bool prof;
   bool l2_next = false;   // the next identity-map conv writes unit-norm rows (the `final` conv of a normalising net)
+  bool wide3 = false;     // 3-D net on neighbour tables: layers with wide-kernel weights run rule-major over the tables' lists
 
   float *ybuf = nullptr;  // per-pair product rows, sized for the largest layer of this forward
 
@@ -509,7 +532,8 @@ struct Fwd {
     a.y = ybuf; a.shift = L.shift;
     a.w = L.w;
     a.cin = L.cin; a.cin_pad = L.cin_pad; a.cout = L.cout; a.cout_pad = L.cout_pad; a.K = L.K;
-    if (km && ms.use_nbr) {
+    const bool wide3_layer = wide3 && km && ms.use_nbr && L.wb && !swapped && km->built;
+    if (km && ms.use_nbr && !wide3_layer) {
       a.pair_in = a.pair_out = a.tile_ptr = a.rule_ptr = nullptr;   // output-stationary path below
       a.tile_desc = nullptr; a.n_rows_dev = nullptr; a.tile_bound = 0;
     } else if (km) {
@@ -535,7 +559,7 @@ struct Fwd {
       if (!e0 || !em || !e1) return DGR_EHIP;
       DGR_HIP_CHECK(hipEventRecord(e0, stream));
     }
-    if (km && ms.use_nbr) {
+    if (km && ms.use_nbr && !wide3_layer) {
       // D = 3: output-stationary fused conv over the dense neighbour table of this (in map, out map) pair
       const DgrNbrTable *t = nullptr;
       for (int l = 0; l < 4; ++l)
@@ -561,6 +585,8 @@ struct Fwd {
       o.w_unscale = L.w_unscale; o.n_in_cap = cin_map.n_cap;
       if (L.w16b && !dgr_exact_f32()) {
         o.row_amax = in.amax;
+        if (in.amax && in.amax_pending)   // the rows came out of a reduction, which leaves no row maxima behind
+          DGR_CHECK(dgr_row_amax(in.ptr, in.ld, L.cin, in.relu, cin_map.n_dev, cin_map.n_cap, in.amax, stream));
         if (!o.row_amax) {   // a tensor that did not come out of one of the conv kernels (the single-layer debug entry)
           uint32_t *mx;
           DGR_ALLOC(mx, ctx->arena, uint32_t, cin_map.n_cap);
@@ -617,6 +643,8 @@ struct Fwd {
                                    out.ptr, out.ld, stream));
     else if (wide) {
       DGR_REQUIRE(in.split.planes, "layer %s: the wide-layer kernel needs its input as split rows", L.name.c_str());
+      if (in.split_pending)   // the rows came out of an output-stationary kernel, which writes f32 rows only
+        DGR_CHECK(dgr_split_rows(in.ptr, in.ld, in.relu, cin_map.n_dev, cin_map.n_cap, in.split, stream));
       if (prof) {   // the kernel stamps its own start / end (dgr_ctx_conv_launch_kernel_us)
         DGR_ALLOC(a.clk, ctx->arena, unsigned long long, 2);
         DGR_HIP_CHECK(hipMemsetAsync(a.clk, 0xff, sizeof(unsigned long long), stream));       // start: atomicMin
@@ -679,7 +707,13 @@ int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, 
   // dense neighbour tables (conv_os.hip).  Any other 3-D shape takes the rule-major two-phase path of conv.hip.
   const bool use_nbr = net->D == 3 && net->cin <= 8 && net->conv1_ks <= 7;
   const bool conv1_fused = use_nbr;
-  DGR_CHECK(dgr_build_maps(A, coords, N, net->D, net->conv1_ks, &f.ms, stream, conv1_fused, /*lean=*/true, use_nbr));
+  // With dgr_net_set_wide_coarse the 128 / 256-channel layers of the two coarse levels run on the wide rule-major kernel
+  // over lists derived from the tables (DGR_NO_WIDE3=1 / DGR_OS_LISTS=1: on the output-stationary kernel after all).  Their product rows
+  // are reserved by the host's bound of 27 pairs per INPUT voxel (the coarse levels' row counts live on the device):
+  // 27 KB per voxel -- forwards beyond 16 GB of that stay on the output-stationary kernel.
+  static const bool no_wide3 = getenv("DGR_NO_WIDE3") != nullptr || getenv("DGR_OS_LISTS") != nullptr;
+  f.wide3 = net->wide_coarse && use_nbr && !no_wide3 && !dgr_exact_f32() && net->W->layers[7].wb && 27 * N * 256 * (int64_t)sizeof(float) <= (16ll << 30);
+  DGR_CHECK(dgr_build_maps(A, coords, N, net->D, net->conv1_ks, &f.ms, stream, conv1_fused, /*lean=*/true, use_nbr, f.wide3));
   if (f.prof) {
     DGR_HIP_CHECK(hipEventRecord(m1, stream));
     (net->D == 3 ? ctx->map3_spans : ctx->map6_spans).push_back({m0, m1});
@@ -689,8 +723,9 @@ int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, 
     const DgrMapSet &m = f.ms;
     int64_t need = m.use_nbr ? 64 : m.conv1.pair_cap * 32;
     const int64_t same_c[4] = {64, 64, 128, 256}, down_c[3] = {64, 128, 256};  // widest Cout per map
-    for (int l = 0; l < 4; ++l) need = std::max(need, m.same[l].pair_cap * same_c[l]);
-    for (int l = 0; l < 3; ++l) need = std::max(need, m.down[l].pair_cap * down_c[l]);
+    // (a 3-D net on neighbour tables has lists -- and product rows -- for the maps of its wide layers only)
+    for (int l = 0; l < 4; ++l) if (m.same[l].built) need = std::max(need, m.same[l].pair_cap * same_c[l]);
+    for (int l = 0; l < 3; ++l) if (m.down[l].built) need = std::max(need, m.down[l].pair_cap * down_c[l]);
     DGR_ALLOC(f.ybuf, A, float, need);
   }
   const DgrMapSet &ms = f.ms;
@@ -733,7 +768,7 @@ int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, 
         {&V4, 14, 128, n4, true}, {&U2, 16, 64, n2, false}, {&V2, 17, 64, n2, true}, {&U1, 19, 64, n1, false},
         {&V1, 20, 64, n1, true}};
     for (auto &e : sp) {
-      if (!net->W->layers[e.consumer].wb) continue;
+      if (!net->W->layers[e.consumer].wb || (net->D == 3 && !f.wide3)) continue;
       e.t->split.channels = e.channels;
       e.t->split_only = e.middle;
       DGR_ALLOC(e.t->split.planes, A, unsigned char, (size_t)e.rows * 4 * e.channels);
@@ -758,6 +793,16 @@ int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, 
     for (Tensor *t : {&T8, &Y8, &S8}) t->amax = take(n8);
     S2.amax2 = CAT2.amax; S2T.amax2 = CAT2.amax;   // both halves of a concatenation feed its row maxima
     S4.amax2 = CAT4.amax; S4T.amax2 = CAT4.amax;
+    if (f.wide3) {
+      // tensors written by a reduction have no row maxima: the two that an output-stationary kernel reads (S8: conv4_tr,
+      // CAT4: conv3_tr) get them from a pass in front of that launch, the others have none (their readers gather split rows)
+      for (Tensor *t : {&Y4, &S4, &T8, &Y8, &V4}) t->amax = nullptr;
+      S4.amax2 = S4T.amax2 = nullptr;
+      S8.amax_pending = CAT4.amax_pending = true;
+      // ... and the two wide-layer inputs that come out of an output-stationary kernel (conv3, conv4_tr) are split in
+      // front of their consumer
+      T4.split_pending = U4.split_pending = true;
+    }
   }
 
   if (use_nbr && !getenv("DGR_NO_DSPLIT")) {
@@ -1002,7 +1047,7 @@ extern "C" int dgr_debug_conv_layer(dgr_ctx *ctx, dgr_net *net, int layer, const
   const int64_t n_cap = f.ms.cm[0].n_cap;
   if (!f.ms.use_nbr) DGR_ALLOC(f.ybuf, A, float, f.ms.same[0].pair_cap * L.cout);
   Tensor tin{const_cast<float *>(in), L.cin, in_relu}, tout{out, L.cout, 0};
-  if (L.wb) {
+  if (L.wb && !f.ms.use_nbr) {
     tin.split.channels = L.cin;
     DGR_ALLOC(tin.split.planes, A, unsigned char, (size_t)n_cap * 4 * L.cin);
     DGR_ALLOC(tin.split.scale, A, float, n_cap);

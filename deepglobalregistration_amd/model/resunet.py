@@ -89,12 +89,13 @@ class ResUNet2:
             share = getattr(self, '_share', None)
             if share is not None:
                 self._net = ops.NetHandle(None, self.D, self.in_channels, self.out_channels, self.conv1_kernel_size,
-                                          self.normalize_feature, self.device, share_from=share._net)
+                                          self.normalize_feature, self.device, share_from=share._net, wide_coarse=self.D == 3)
                 return self._net
             if self._state is None:
                 raise RuntimeError('load_state_dict() must be called before the first forward')
             self._net = ops.NetHandle(self._state, self.D, self.in_channels, self.out_channels,
-                                      self.conv1_kernel_size, self.normalize_feature, self.device)
+                                      self.conv1_kernel_size, self.normalize_feature, self.device,
+                                      wide_coarse=self.D == 3)   # the product's FCGF net: coarse levels on the wide kernel
         return self._net
 
     def forward(self, x):

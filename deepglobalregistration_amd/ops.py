@@ -59,8 +59,10 @@ class NetHandle:
     another reading -- `ResUNet2.load_state_dict` does that, this class and the C API do not)."""
 
     def __init__(self, state_dict, D, in_channels, out_channels, conv1_kernel_size,
-                 normalize_feature, device='cuda', share_from=None):
+                 normalize_feature, device='cuda', share_from=None, wide_coarse=False):
+        # wide_coarse (D = 3): dgr_net_set_wide_coarse -- the coarse levels' 128 / 256-channel layers on the wide kernel
         lib = _lib.load()
+        self.wide_coarse = bool(wide_coarse)
         self.device = torch.device(device)
         self.D, self.cin, self.cout = D, in_channels, out_channels
         self.conv1_ks, self.normalize = int(conv1_kernel_size), bool(normalize_feature)
@@ -73,6 +75,7 @@ class NetHandle:
             with torch.cuda.device(self.device):
                 check(lib.dgr_net_share(get_ctx(self.device), share_from.handle, C.byref(h)))
             self.handle = h
+            check(lib.dgr_net_set_wide_coarse(h, int(self.wide_coarse)))
             return
         keep, descs = [], []
         items = [(n, t) for n, t in state_dict.items() if not n.endswith('num_batches_tracked')]
@@ -102,6 +105,8 @@ class NetHandle:
                          conv1_kernel_size, int(bool(normalize_feature)), arr, len(descs),
                          C.byref(h)))
         self.handle = h
+        if self.wide_coarse:
+            check(lib.dgr_net_set_wide_coarse(h, 1))
 
     def __del__(self):
         try:
@@ -202,17 +207,21 @@ class NetHandle:
 # ----------------------------------------------------------------------------
 class Maps:
     """Coordinate maps + kernel maps of one sparse tensor (inspection / parity tests).  lean=True builds the object
-    exactly as a network forward builds its own maps (dgr_maps_create_ex, DGR_MAPS_LEAN)."""
+    exactly as a network forward builds its own maps (dgr_maps_create_ex, DGR_MAPS_LEAN); nbr_lists=True (lean, D = 3)
+    adds the rule-major lists the forward of a 3-D net derives from its neighbour tables for its 128 / 256-channel
+    layers (DGR_MAPS_NBR_LISTS: 'same' at ts 4 and 8, 'down' at ts 4)."""
 
-    def __init__(self, coords, D, conv1_kernel_size=3, device='cuda', lean=False):
+    def __init__(self, coords, D, conv1_kernel_size=3, device='cuda', lean=False, nbr_lists=False):
         lib = _lib.load()
         self.device = torch.device(device)
         coords = _as(coords, torch.int32, self.device)
         self.D, self.lean = D, bool(lean)
         h = vp()
         if lean:
-            check(lib.dgr_maps_create_ex(get_ctx(self.device), ptr(coords), coords.shape[0], D, conv1_kernel_size, 1,
-                                         C.byref(h), stream_ptr(self.device.index)))
+            check(lib.dgr_maps_create_ex(get_ctx(self.device), ptr(coords), coords.shape[0], D, conv1_kernel_size,
+                                         1 | (2 if nbr_lists else 0), C.byref(h), stream_ptr(self.device.index)))
+        elif nbr_lists:
+            raise ValueError('nbr_lists goes with lean=True')
         else:
             check(lib.dgr_maps_create(get_ctx(self.device), ptr(coords), coords.shape[0], D, conv1_kernel_size,
                                       C.byref(h), stream_ptr(self.device.index)))

@@ -124,6 +124,14 @@ int64_t dgr_net_param_bytes(const dgr_net *net);
  * dgr_net_param_bytes reports the shared set's bytes (count it once per distinct weight set). */
 int dgr_net_share(dgr_ctx *ctx, const dgr_net *src, dgr_net **out);
 int dgr_net_sharers(const dgr_net *net);
+/* D = 3 nets with at most 8 input channels (FCGF): on != 0 -- the forwards of THIS net object run the K = 27 layers with
+ * 128 / 256 channels on both sides (block3, block4, block4_tr, conv4) on the wide rule-major kernel over lists derived
+ * from the neighbour tables, instead of the output-stationary kernel.  Faster on the coarse levels (few rows, many pairs);
+ * results agree to a few f32 ulps of a tensor's scale, not bit for bit.  Around those layers dgr_net_get_tensor then
+ * serves split rows (T4, Y4, S4, T8, Y8, U4, V4; Y4, Y8, V4 as split rows only) and no row maxima for Y4, S4, T8, Y8,
+ * V4.  Off (the default): every tensor as documented below.  dgr_net_share copies the setting.  DGR_NO_WIDE3=1 in the
+ * environment overrides it to off. */
+int dgr_net_set_wide_coarse(dgr_net *net, int on);
 
 /* ---- sparse ResUNet forward: replaces ME.SparseTensor(feats, coordinates=coords) +
  * ResUNet2.forward (core/deep_global_registration.py:163-169, 210-217; model/resunet.py:598-649).
@@ -187,6 +195,10 @@ int dgr_maps_get_kernel_map(dgr_maps *maps, int kind, int ts, int32_t *rule_ptr,
  * dgr_maps_create.  The translating getters above need pair_out: on a lean object they serve the coordinates, the
  * neighbour tables and the strided maps only. */
 #define DGR_MAPS_LEAN 1
+/* with DGR_MAPS_LEAN, D = 3: also what the forward of a 3-D net adds for its 128 / 256-channel layers -- lean rule-major
+ * maps "same" at ts 4 and 8 and "down" at ts 4, derived from the neighbour tables (rule_ptr, pair_in, out_ptr, out_pos,
+ * tile_ptr, tile_desc; no pair_out, no pair_k, no in-major CSR: the transposed conv of that map runs on "nbr_up") */
+#define DGR_MAPS_NBR_LISTS 2
 int dgr_maps_create_ex(dgr_ctx *ctx, const int32_t *coords, int64_t N, int D, int conv1_kernel_size, int flags,
                        dgr_maps **out, dgr_stream stream);
 /* Test instrument: ONE array of a built maps object copied to the host as it lies in memory -- the library's own row
