@@ -117,6 +117,7 @@ SIGNATURES = {
                                             c_f64p, c_f64p, vp]),
     'dgr_debug_smooth_l1': (C.c_int, [vp, vp, vp, C.c_int64, C.c_float, vp, vp]),
     'dgr_debug_conv_layer': (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int64, vp, vp]),
+    'dgr_debug_workspace_peek': (C.c_int, [vp, C.c_int64, C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

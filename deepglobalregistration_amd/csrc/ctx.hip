@@ -24,6 +24,27 @@ extern "C" const char *dgr_version(void) { return "dgr_hip 0.4 (gfx950)"; }
 static constexpr size_t kAlign = 256;
 static constexpr size_t kMinChunk = (size_t)256 << 20;
 
+// DGR_WORKSPACE_FILL=<32-bit hex word> (test switch, read once per process): every private device allocation of the
+// library starts out holding that word, and so does the context's arena after every reset -- a result that depends on memory
+// a call was given but has not written then changes with the word (tests/test_gpu_workspace_poison.py).  Unset: nothing runs.
+bool dgr_workspace_fill(uint32_t *word) {
+  static const char *env = getenv("DGR_WORKSPACE_FILL");
+  static const uint32_t w = env ? (uint32_t)strtoul(env, nullptr, 16) : 0u;
+  if (word) *word = w;
+  return env != nullptr;
+}
+
+// debug mode: synchronises the device on both sides, so that the fill is ordered against every stream
+int dgr_fill_fresh(void *p, size_t bytes) {
+  uint32_t w;
+  if (!dgr_workspace_fill(&w) || !p || bytes == 0) return DGR_OK;
+  DGR_HIP_CHECK(hipDeviceSynchronize());
+  if (bytes / 4) DGR_HIP_CHECK(hipMemsetD32((hipDeviceptr_t)p, (int)w, bytes / 4));
+  if (bytes % 4) DGR_HIP_CHECK(hipMemcpy((char *)p + bytes / 4 * 4, &w, bytes % 4, hipMemcpyHostToDevice));
+  DGR_HIP_CHECK(hipDeviceSynchronize());
+  return DGR_OK;
+}
+
 void *DgrArena::alloc(size_t bytes) {
   bytes = (bytes + kAlign - 1) / kAlign * kAlign;
   if (bytes == 0) bytes = kAlign;
@@ -46,6 +67,10 @@ void *DgrArena::alloc(size_t bytes) {
   hipError_t e = hipMalloc((void **)&base, sz);
   if (e != hipSuccess) {
     dgr_set_error("workspace hipMalloc(%zu MiB) failed: %s", sz >> 20, hipGetErrorString(e));
+    return nullptr;
+  }
+  if (dgr_fill_fresh(base, sz) != DGR_OK) {
+    (void)hipFree(base);
     return nullptr;
   }
   chunks.push_back({base, sz});
@@ -77,6 +102,7 @@ int DgrArena::reset() {
     }
     chunks.push_back({base, want});
   }
+  for (auto &c : chunks) DGR_CHECK(dgr_fill_fresh(c.base, c.size));
   cur = 0;
   offset = 0;
   used_total = 0;
@@ -236,6 +262,18 @@ extern "C" void dgr_ctx_destroy(dgr_ctx *ctx) {
 
 extern "C" int64_t dgr_ctx_workspace_bytes(dgr_ctx *ctx) {
   return ctx ? (int64_t)ctx->arena.reserved() : 0;
+}
+
+// test instrument: what a kernel of the next call would find in its scratch
+extern "C" int dgr_debug_workspace_peek(dgr_ctx *ctx, int64_t nwords, uint32_t *host_out) {
+  DGR_REQUIRE(ctx != nullptr && host_out != nullptr && nwords > 0, "dgr_debug_workspace_peek: bad argument");
+  DGR_HIP_CHECK(hipSetDevice(ctx->device));
+  DGR_HIP_CHECK(hipDeviceSynchronize());
+  DGR_CHECK(ctx->arena.reset());
+  uint32_t *p;
+  DGR_ALLOC(p, ctx->arena, uint32_t, nwords);
+  DGR_HIP_CHECK(hipMemcpy(host_out, p, (size_t)nwords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return DGR_OK;
 }
 
 extern "C" int dgr_ctx_set_profiling(dgr_ctx *ctx, int enable) {

@@ -48,6 +48,12 @@ inline bool dgr_exact_f32() {
   return on;
 }
 
+// DGR_WORKSPACE_FILL=<32-bit hex word> (ctx.hip; read once per process): true when set, *word (nullable) = the word.
+bool dgr_workspace_fill(uint32_t *word);
+// ... and, when it is set, fills a fresh private device allocation with the word before anything writes it (device-
+// synchronising; a no-op returning DGR_OK when unset).  DgrArena fills its own chunks: call this for every other hipMalloc.
+int dgr_fill_fresh(void *p, size_t bytes);
+
 // ------------------------------------------------------------------------------------------
 // grow-only device arena (reset at the start of every top-level call)
 // ------------------------------------------------------------------------------------------
@@ -69,8 +75,8 @@ struct DgrArena {
   // stack discipline: memory handed out after `m` is reused by later allocations; safe for work
   // enqueued on ONE stream (stream order separates the old and the new users)
   void rewind(const Mark &m) { cur = m.cur; offset = m.offset; used_total = m.used_total; }
-  void *alloc(size_t bytes);  // nullptr on failure (error set)
-  int reset();                // coalesces into one chunk when the last call spilled
+  void *alloc(size_t bytes);  // nullptr on failure (error set); a new chunk starts out filled under DGR_WORKSPACE_FILL
+  int reset();                // coalesces into one chunk when the last call spilled; refills under DGR_WORKSPACE_FILL
   void release();
   size_t reserved() const;
   template <typename T>

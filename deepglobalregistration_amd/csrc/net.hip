@@ -91,6 +91,7 @@ struct DgrWeights {
   template <class T> int alloc(T **p, size_t n) {
     DGR_HIP_CHECK(hipMalloc((void **)p, n * sizeof(T)));
     allocs.push_back(*p);
+    DGR_CHECK(dgr_fill_fresh(*p, n * sizeof(T)));
     return DGR_OK;
   }
   // Runs on whichever host thread drops the last reference (e.g. Python's GC inside a worker thread): the thread's current
@@ -235,6 +236,7 @@ static int make_layer(dgr_net *net, WeightPrep &P, const dgr_weight_desc *descs,
       DGR_HIP_CHECK(hipFree(P.staging));
       P.staging = nullptr;
       DGR_HIP_CHECK(hipMalloc((void **)&P.staging, n * sizeof(float)));
+      DGR_CHECK(dgr_fill_fresh(P.staging, n * sizeof(float)));
       P.staging_n = n;
     }
     DGR_HIP_CHECK(hipMemcpyAsync(P.staging, kd->data, n * sizeof(float), hipMemcpyHostToDevice, s));
@@ -409,6 +411,8 @@ static int net_create(dgr_ctx *ctx, int D, int in_channels, int out_channels, in
   DGR_HIP_CHECK(hipStreamCreate(&P.s));
   DGR_HIP_CHECK(hipMalloc((void **)&P.sc, 256 * sizeof(float)));
   DGR_HIP_CHECK(hipMalloc((void **)&P.mxb, sizeof(uint32_t)));
+  DGR_CHECK(dgr_fill_fresh(P.sc, 256 * sizeof(float)));
+  DGR_CHECK(dgr_fill_fresh(P.mxb, sizeof(uint32_t)));
   dgr_net *net = new dgr_net();
   net->ctx = ctx;
   net->W = std::make_shared<DgrWeights>();

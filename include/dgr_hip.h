@@ -634,6 +634,12 @@ int dgr_debug_smooth_l1(dgr_ctx *ctx, const float *X, const float *Y, int64_t n,
 int dgr_debug_conv_layer(dgr_ctx *ctx, dgr_net *net, int layer, const int32_t *coords, const float *in, int in_relu,
                          int64_t N, float *out, dgr_stream stream);
 
+/* Test instrument of the DGR_WORKSPACE_FILL=<32-bit hex word> switch (read once per process; when set, every private device
+ * allocation of the library and the context's workspace at the start of every call hold that word): resets the context's
+ * workspace, takes nwords 32-bit words from its start, writes nothing to them and copies them to host_out [nwords] (HOST).
+ * Synchronises the device. */
+int dgr_debug_workspace_peek(dgr_ctx *ctx, int64_t nwords, uint32_t *host_out);
+
 #ifdef __cplusplus
 }
 #endif
