@@ -118,6 +118,8 @@ SIGNATURES = {
     'dgr_debug_smooth_l1': (C.c_int, [vp, vp, vp, C.c_int64, C.c_float, vp, vp]),
     'dgr_debug_conv_layer': (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int64, vp, vp]),
     'dgr_debug_workspace_peek': (C.c_int, [vp, C.c_int64, C.POINTER(C.c_uint32)]),
+    'dgr_ctx_set_knn_trace': (C.c_int, [vp, C.c_int]),
+    'dgr_debug_knn_trace': (C.c_int, [vp, c_i32p, C.c_int64, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

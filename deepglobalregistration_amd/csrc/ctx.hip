@@ -276,6 +276,24 @@ extern "C" int dgr_debug_workspace_peek(dgr_ctx *ctx, int64_t nwords, uint32_t *
   return DGR_OK;
 }
 
+// test instrument: which kernels searched each pair of the last k-NN call (csrc/knn_common.h: knn_trace_table)
+extern "C" int dgr_ctx_set_knn_trace(dgr_ctx *ctx, int enable) {
+  DGR_REQUIRE(ctx != nullptr, "ctx is NULL");
+  ctx->knn_trace = enable != 0;
+  ctx->knn_trace_rows.clear();
+  return DGR_OK;
+}
+
+extern "C" int dgr_debug_knn_trace(dgr_ctx *ctx, int32_t *host_out, int64_t capacity_rows, int64_t *nrows) {
+  DGR_REQUIRE(ctx != nullptr && nrows != nullptr && capacity_rows >= 0 && (host_out != nullptr || capacity_rows == 0),
+              "dgr_debug_knn_trace: bad argument");
+  const int64_t n = (int64_t)(ctx->knn_trace_rows.size() / DGR_KNN_TRACE_FIELDS);
+  const int64_t m = n < capacity_rows ? n : capacity_rows;
+  if (m > 0) memcpy(host_out, ctx->knn_trace_rows.data(), (size_t)m * DGR_KNN_TRACE_FIELDS * sizeof(int32_t));
+  *nrows = n;
+  return DGR_OK;
+}
+
 extern "C" int dgr_ctx_set_profiling(dgr_ctx *ctx, int enable) {
   DGR_REQUIRE(ctx != nullptr, "ctx is NULL");
   ctx->profiling = enable != 0;

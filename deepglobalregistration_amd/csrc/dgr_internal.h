@@ -306,6 +306,8 @@ struct DgrEventPool {  // HIP events bracketing the conv kernels when profiling 
   void release();
 };
 
+constexpr int DGR_KNN_TRACE_FIELDS = 8;   // words per row of dgr_debug_knn_trace (include/dgr_hip.h)
+
 struct dgr_ctx {
   int device = 0;
   int num_cus = 256;
@@ -335,6 +337,11 @@ struct dgr_ctx {
   // dgr_ctx_create_partition_stream: the context's own CU-masked stream; num_cus is then the share, all_cus the device
   hipStream_t part_stream = nullptr;
   int all_cus = 256;
+  // dgr_ctx_set_knn_trace: the route every pair of the last k-NN call took, DGR_KNN_TRACE_FIELDS words per pair
+  // (knn_common.h); off: untouched
+  bool knn_trace = false;
+  std::vector<int32_t> knn_trace_rows;
+  std::vector<int64_t> knn_trace_q0;   // first query row of the pairs of the table being traced (finds a pair's row)
 };
 
 // at least `bytes` of pinned host memory owned by the context (grows; contents are not preserved across a growth -- ask

@@ -247,7 +247,8 @@ static int knn_prefiltered(dgr_ctx *ctx, const float *F0, const float *F1, KnnBa
   DGR_LAUNCH_CHECK();
   DGR_CHECK(knn_launch<32>(ctx, F0, F1, B, best, P.flags, stream, P.qlist, P.qcount, P.q_begin));
   // non-finite / huge input: the brute-force kernel redoes the pair's whole search
-  return knn_launch<32>(ctx, F0, F1, B, best, P.fallback, stream);
+  DGR_CHECK(knn_launch<32>(ctx, F0, F1, B, best, P.fallback, stream));
+  return knn_trace_prefiltered(ctx, B, P, stream);
 }
 
 // Batched entry of the fused pipeline: pair p = rows off0[p] .. off0[p + 1] of F0 against rows off1[p] .. off1[p + 1] of

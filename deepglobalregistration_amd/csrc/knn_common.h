@@ -99,6 +99,21 @@ inline int knn_enter(const char *entry, dgr_ctx *ctx, const void *F0, const void
   return ctx->arena.reset();
 }
 
+// Opt-in route trace (dgr_ctx_set_knn_trace, read back by dgr_debug_knn_trace; a test instrument).  One row of
+// DGR_KNN_TRACE_FIELDS = 8 words per pair of the last call: {pair of the call, table, route (0 brute force / 1 prefiltered),
+// fallback flag, overflow list length, redo-by-brute-force flag, largest cand_cnt, queries with cand_cnt == 0}.
+// knn_trace_table opens the rows of a table, all on route 0; knn_trace_prefiltered (knn_prefilter.h) fills in the pairs
+// of its prefiltered sub-batch.  With the trace off neither runs: a call issues the launches and copies it always did.
+inline void knn_trace_table(dgr_ctx *ctx, const KnnBatch &B, int p0) {
+  if (p0 == 0) ctx->knn_trace_rows.clear();
+  ctx->knn_trace_q0.clear();
+  for (int p = 0; p < B.np; ++p) {
+    const int32_t row[DGR_KNN_TRACE_FIELDS] = {p0 + p, p0 / KNN_MAXP, 0, 0, 0, 0, 0, 0};
+    ctx->knn_trace_rows.insert(ctx->knn_trace_rows.end(), row, row + DGR_KNN_TRACE_FIELDS);
+    ctx->knn_trace_q0.push_back(B.p[p].q0);
+  }
+}
+
 // Pairs = row ranges off0 / off1 (host arrays) of the concatenated F0 / F1.  Allocates the result keys (k per query row;
 // `clear`: set to KNN_KEY_NONE, for a search that merges into them), cuts the pairs into descriptor tables of KNN_MAXP
 // and runs fn(table, keys) for each, its scratch taken from the arena and given back afterwards.
@@ -123,6 +138,7 @@ inline int knn_for_each_table(dgr_ctx *ctx, const int64_t *off0, const int64_t *
                   d.n1);
     }
     const DgrArena::Mark mk = ctx->arena.mark();
+    if (ctx->knn_trace) knn_trace_table(ctx, B, p0);
     DGR_CHECK(fn(B, keys));
     ctx->arena.rewind(mk);
   }

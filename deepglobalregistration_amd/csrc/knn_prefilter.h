@@ -381,6 +381,39 @@ inline int knn_mfma_launch(dgr_ctx *ctx, const KnnBatch &B, const KnnPlan &P, in
   return DGR_OK;
 }
 
+// Route trace of a prefiltered table, called by the searches behind their last launch and BEFORE the arena is rewound:
+// waits for the stream, copies cand_cnt and the per-pair words behind it to the host and reduces them into the rows
+// knn_trace_table opened (the pair words are indexed by the pair's position in B, the prefiltered sub-batch).
+inline int knn_trace_prefiltered(dgr_ctx *ctx, const KnnBatch &B, const KnnPlan &P, hipStream_t stream) {
+  if (!ctx->knn_trace) return DGR_OK;
+  std::vector<int32_t> host((size_t)(P.span + 4 * KNN_MAXP));
+  DGR_HIP_CHECK(hipStreamSynchronize(stream));
+  DGR_HIP_CHECK(hipMemcpy(host.data(), P.cand_cnt, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  const int32_t *words = host.data() + P.span;
+  const size_t n_table = ctx->knn_trace_q0.size();
+  int32_t *rows = ctx->knn_trace_rows.data() + (ctx->knn_trace_rows.size() - n_table * DGR_KNN_TRACE_FIELDS);
+  for (int p = 0; p < B.np; ++p) {
+    const KnnPair &d = B.p[p];
+    size_t t = 0;
+    while (t < n_table && ctx->knn_trace_q0[t] != d.q0) ++t;
+    DGR_REQUIRE(t < n_table, "find_knn: trace row of a prefiltered pair not found");
+    int32_t cnt_max = 0, n_zero = 0;
+    for (int64_t q = 0; q < d.n0; ++q) {
+      const int32_t c = host[(size_t)(d.q0 - P.q_begin + q)];
+      cnt_max = std::max(cnt_max, c);
+      n_zero += c == 0;
+    }
+    int32_t *row = rows + t * DGR_KNN_TRACE_FIELDS;
+    row[2] = 1;
+    row[3] = words[KNN_MAXP + p];
+    row[4] = words[2 * KNN_MAXP + p];
+    row[5] = words[3 * KNN_MAXP + p];
+    row[6] = cnt_max;
+    row[7] = n_zero;
+  }
+  return DGR_OK;
+}
+
 // knn.hip: lists the queries with more than `slots` candidates -- P.qlist[q0 - q_begin + n] = their row inside the pair,
 // P.qcount[pair] = n -- for the search's fallback kernels
 int knn_list_overflows(const KnnBatch &B, const KnnPlan &P, int slots, hipStream_t stream);

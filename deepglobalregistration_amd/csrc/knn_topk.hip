@@ -303,7 +303,8 @@ static int knn_topk_prefiltered(dgr_ctx *ctx, const float *F0, const float *F1, 
   knn_topk_scan_kernel<K><<<sgrid, 256, 0, stream>>>(F0, F1, B, k, P.q_begin, P.qlist, P.qcount, keys);
   knn_topk_redo_flags<<<1, 64, 0, stream>>>(P.fallback, P.qcount, B.np, P.flags);
   DGR_LAUNCH_CHECK();
-  return knn_topk_brute<32, K>(ctx, F0, F1, B, k, keys, P.flags, stream);
+  DGR_CHECK((knn_topk_brute<32, K>(ctx, F0, F1, B, k, keys, P.flags, stream)));
+  return knn_trace_prefiltered(ctx, B, P, stream);
 }
 
 template <int K>

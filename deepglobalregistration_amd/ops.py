@@ -365,6 +365,43 @@ def knn_batch(F0, F1, off0, off1, k, squared=False, return_distance=False):
     return (idx, dist) if return_distance else idx
 
 
+KNN_TRACE_FIELDS = ('pair', 'table', 'route', 'fallback', 'list_len', 'redo', 'cand_max', 'cand_zero')
+
+
+def _trace_device(device):
+    """The CUDA(ROCm) device of a trace call; ValueError for anything else, before any device state exists."""
+    if isinstance(device, (bool, int, float)) or device is None or torch.is_tensor(device):
+        raise ValueError(f'expected a device such as "cuda:0", got {device!r}')
+    try:
+        dev = torch.device(device)
+    except (RuntimeError, TypeError) as e:
+        raise ValueError(f'expected a device such as "cuda:0", got {device!r}') from e
+    if dev.type != 'cuda':
+        raise ValueError(f'the k-NN trace lives on a GPU context, got device {dev}')
+    return dev
+
+
+def knn_trace(device, enable):
+    """Switch the route trace of the k-NN searches of this thread's context (dgr_ctx_set_knn_trace): a test instrument.
+    Off (the default) a search issues exactly the launches it always did; on, every prefiltered table waits for its
+    stream and is reduced on the host."""
+    dev = _trace_device(device)
+    check(_lib.load().dgr_ctx_set_knn_trace(get_ctx(dev), int(bool(enable))))
+
+
+def knn_trace_rows(device):
+    """int32 [npairs, 8] (numpy): one row per pair of the last traced k-NN call on this thread's context, columns
+    KNN_TRACE_FIELDS (dgr_debug_knn_trace)."""
+    dev = _trace_device(device)
+    lib = _lib.load()
+    n = C.c_int64(0)
+    check(lib.dgr_debug_knn_trace(get_ctx(dev), None, 0, C.byref(n)))
+    rows = np.zeros((n.value, len(KNN_TRACE_FIELDS)), np.int32)
+    if n.value:
+        check(lib.dgr_debug_knn_trace(get_ctx(dev), rows.ctypes.data_as(_lib.c_i32p), n.value, C.byref(n)))
+    return rows
+
+
 def inlier_inputs(coords0, xyz0, coords1, xyz1, idx1, feature_type='coords'):
     lib = _lib.load()
     dev = _dev(xyz0)

@@ -640,6 +640,20 @@ int dgr_debug_conv_layer(dgr_ctx *ctx, dgr_net *net, int layer, const int32_t *c
  * Synchronises the device. */
 int dgr_debug_workspace_peek(dgr_ctx *ctx, int64_t nwords, uint32_t *host_out);
 
+/* Test instrument: the route trace of the feature-space k-NN searches.  Off by default, and then a search issues exactly
+ * the launches and copies it always did.  On (enable != 0): after every prefiltered descriptor table of a k-NN call on
+ * this context -- dgr_knn1_l2 / dgr_knn_l2, their _batch forms, and the search inside dgr_register_batch /
+ * dgr_register_pairs -- the library waits for the stream and reduces the table's per-pair words and candidate counts
+ * on the host.  Switching clears the recorded rows. */
+int dgr_ctx_set_knn_trace(dgr_ctx *ctx, int enable);
+/* One row of 8 int32 per pair of the last traced k-NN call, in call order, into host_out [capacity_rows][8] (HOST; at
+ * most capacity_rows rows are written, NULL allowed with capacity_rows == 0); *nrows = the rows the call recorded.
+ * Fields: pair index in the call; descriptor table (32 pairs each); route, 0 = brute force (C = 16 / 64, a small
+ * reference set, DGR_KNN_BRUTE), 1 = bf16 prefilter; then, for route 1 (0 otherwise): fallback flag (non-finite / huge
+ * input), length of the overflow list, redo-by-brute-force flag, largest candidate count over the pair's queries,
+ * number of its queries without a candidate. */
+int dgr_debug_knn_trace(dgr_ctx *ctx, int32_t *host_out, int64_t capacity_rows, int64_t *nrows);
+
 #ifdef __cplusplus
 }
 #endif
