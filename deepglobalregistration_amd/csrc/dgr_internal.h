@@ -404,4 +404,23 @@ struct DgrRegResult {  // device-side result record of the registration kernel
   int32_t status;
   int32_t pad;
 };
+// reg.hip: the registration kernel over a batch of pairs, on the context's arena
+int dgr_registration_launch_ctx(dgr_ctx *ctx, const float *xyz0, const float *xyz1, const int64_t *idx1,
+                                const float *lw, int is_logit, float clip, const int64_t *off0_dev,
+                                const int64_t *off0_host, int npairs, int64_t total_rows, float q, int max_iter, int max_break,
+                                double ratio, int skip_refine, int gate, float eps, float *weights_out,
+                                DgrRegResult *results_dev, hipStream_t stream);
+// net.hip: the error flag word of a top-level call (a fresh one in the arena / read back, which synchronises the stream)
+int dgr_ctx_new_flag(dgr_ctx *ctx, hipStream_t stream);
+int dgr_ctx_check_flag(dgr_ctx *ctx, hipStream_t stream);
+// ... and what the fused pipeline asks a net
+int dgr_net_out_channels(const dgr_net *net);
+int dgr_net_in_channels(const dgr_net *net);
+int dgr_net_dim(const dgr_net *net);
+const dgr_ctx *dgr_net_ctx(const dgr_net *net);
+void dgr_net_invalidate_runs(dgr_net *net);   // it rewinds the arena region of a forward: the net's read-backs refuse
+// coordmap.hip: the two steps of dgr_build_maps in front of the kernel maps
+int dgr_build_coord_maps(DgrArena &arena, const int32_t *coords, int64_t N, DgrMapSet *ms, hipStream_t stream);
+int dgr_build_half_buckets(DgrArena &arena, DgrCoordMap *cm, DgrHalfBuckets *hb, int levels, int renumber_from,
+                           hipStream_t stream);
 static inline int64_t dgr_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

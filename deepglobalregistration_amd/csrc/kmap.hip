@@ -1074,10 +1074,6 @@ static int build_nbr_lists3(DgrArena &arena, const NbrListSpec *specs, int nj, h
   return DGR_OK;
 }
 
-int dgr_build_coord_maps(DgrArena &arena, const int32_t *coords, int64_t N, DgrMapSet *ms,
-                         hipStream_t stream);
-int dgr_build_half_buckets(DgrArena &arena, DgrCoordMap *cm, DgrHalfBuckets *hb, int levels, int renumber_from, hipStream_t stream);
-
 int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int conv1_ks,
                    DgrMapSet *ms, hipStream_t stream, bool skip_conv1_map, bool lean, bool nbr_tables, bool nbr_lists) {
   DGR_REQUIRE(D == 3 || D == 6, "D=%d not supported (the DGR path uses D=3 and D=6)", D);
@@ -1121,7 +1117,7 @@ int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int
     }
     if (lean && nbr_lists) {
       // ... plus rule-major lists of the two coarse same-stride tables and the level 2 -> 3 strided one: the 128 / 256-channel
-      // layers there run on the wide rule-major kernel (net.hip, Fwd::conv)
+      // layers there run on the wide rule-major kernel (net.hip, layer_kind)
       const NbrListSpec specs[3] = {{&ms->nsame[2], &ms->cm[2], &ms->same[2]}, {&ms->nsame[3], &ms->cm[3], &ms->same[3]},
                                     {&ms->ndown[2], &ms->cm[3], &ms->down[2]}};
       DGR_CHECK(build_nbr_lists3(arena, specs, 3, stream));

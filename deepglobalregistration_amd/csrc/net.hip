@@ -5,8 +5,8 @@
 //
 // Load time: eval-mode batch norm is folded into the kernels (scale) and a per-channel shift; the
 // kernels are re-tiled on the device into the MFMA B-operand order documented in conv.hip.
-// Forward: every conv is one of the kernel families of conv.hip / conv_os.hip / conv_wide.hip (chosen per layer in
-// Fwd::conv); rule-major layers write per-pair product rows that a deterministic reduction sums on top of the folded
+// Forward: a loop over the layer table; every conv is one of the kernel families of conv.hip / conv_os.hip /
+// conv_wide.hip (chosen per layer in layer_kind); rule-major layers write per-pair product rows that a deterministic reduction sums on top of the folded
 // shift (+ residual).  ReLU is never a separate pass: a tensor carries a "ReLU pending" flag and the consumer applies
 // max(x,0) while gathering (or the producer bakes it into the split rows it writes for a wide-layer consumer).
 // ME.cat is free: producers write into column ranges of a pre-concatenated buffer (row stride = total channels).
@@ -15,15 +15,78 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
 #include <memory>
 #include <string>
 
 #include "dgr_internal.h"
 
-static const int CH[5] = {0, 32, 64, 128, 256};     // model/resunet.py:664
-static const int TR[5] = {0, 64, 64, 64, 128};      // model/resunet.py:665
+constexpr int CH[5] = {0, 32, 64, 128, 256};     // model/resunet.py:664
+constexpr int TR[5] = {0, 64, 64, 64, 128};      // model/resunet.py:665
 static constexpr float BN_EPS = 1e-5f;
+
+// ---- the forward as data (model/resunet.py:598-649; tests/layer_trace_ref.py holds the same two tables)
+// Tensors: level = log2 of the tensor stride; `buf` = the row that owns the buffer (its own index, or the concatenation
+// this tensor is the columns [col0, col0 + cols) of: ME.cat is free, producers write into column ranges of a
+// pre-concatenated buffer); the row stride is the owner's width; relu = consumers apply max(x, 0) when reading.
+// Owners are allocated in table order, and stand in front of the rows that alias them.
+enum Tn : int { NO = -1, X, T1, Y1, CAT1, S1T, S1, T2, Y2, CAT2, S2T, S2, T4, Y4, CAT4, S4T, S4, T8, Y8, S8,
+                U4, V4, U2, V2, U1, V1, H, OUT, N_TENSORS };
+constexpr int W_CIN = -1, W_COUT = -2;   // widths the caller chooses (dgr_net::cin / cout)
+struct TensorRow { const char *name; int lvl; Tn buf; int col0, cols, relu; };
+static const TensorRow TENSORS[N_TENSORS] = {
+    {"X", 0, X, 0, W_CIN, 0},   // the caller's features
+    {"T1", 0, T1, 0, CH[1], 0}, {"Y1", 0, Y1, 0, CH[1], 1},
+    {"CAT1", 0, CAT1, 0, TR[2] + CH[1], 1}, {"S1T", 0, CAT1, 0, TR[2], 1}, {"S1", 0, CAT1, TR[2], CH[1], 1},
+    {"T2", 1, T2, 0, CH[2], 0}, {"Y2", 1, Y2, 0, CH[2], 1},
+    {"CAT2", 1, CAT2, 0, TR[3] + CH[2], 1}, {"S2T", 1, CAT2, 0, TR[3], 1}, {"S2", 1, CAT2, TR[3], CH[2], 1},
+    {"T4", 2, T4, 0, CH[3], 0}, {"Y4", 2, Y4, 0, CH[3], 1},
+    {"CAT4", 2, CAT4, 0, TR[4] + CH[3], 1}, {"S4T", 2, CAT4, 0, TR[4], 1}, {"S4", 2, CAT4, TR[4], CH[3], 1},
+    {"T8", 3, T8, 0, CH[4], 0}, {"Y8", 3, Y8, 0, CH[4], 1}, {"S8", 3, S8, 0, CH[4], 1},
+    {"U4", 2, U4, 0, TR[4], 0}, {"V4", 2, V4, 0, TR[4], 1},
+    {"U2", 1, U2, 0, TR[3], 0}, {"V2", 1, V2, 0, TR[3], 1},
+    {"U1", 0, U1, 0, TR[2], 0}, {"V1", 0, V1, 0, TR[2], 1},
+    {"H", 0, H, 0, TR[1], 1},
+    {"OUT", 0, OUT, 0, W_COUT, 0}};   // the caller's output (a buffer of the forward's while it is not normalised yet)
+// ... and the block outputs that dgr_net_get_intermediate serves (as f32 rows, ReLU applied), by their names in the model
+static const struct { const char *name; Tn t; } INTERMEDIATES[] = {
+    {"s1", S1}, {"s2", S2}, {"s4", S4}, {"s8", S8}, {"s4_tr", S4T}, {"s2_tr", S2T}, {"s1_tr", S1T}};
+
+// Layers in forward order.  The map says which kernel map and which kernel volume: conv1's ks^D at stride 1; the 3^D
+// map of the tensors' level (same), into the next coarser level (down), or that one with in / out swapped (up: the
+// transposed convs); none (identity, kernel volume 1).  A layer's Cin / Cout are its tensors' widths.
+enum Map : int { M_CONV1, M_SAME, M_DOWN, M_UP, M_IDENT };
+struct LayerRow { const char *name, *norm; bool bias; Map map; Tn in, out, res; };
+#define DGR_BLOCK(b, a, y, s) {b ".conv1", b ".norm1", false, M_SAME, a, y, NO}, {b ".conv2", b ".norm2", false, M_SAME, y, s, a}
+static const LayerRow LAYERS[] = {
+    {"conv1", "norm1", false, M_CONV1, X, T1, NO},             DGR_BLOCK("block1", T1, Y1, S1),
+    {"conv2", "norm2", false, M_DOWN, S1, T2, NO},             DGR_BLOCK("block2", T2, Y2, S2),
+    {"conv3", "norm3", false, M_DOWN, S2, T4, NO},             DGR_BLOCK("block3", T4, Y4, S4),
+    {"conv4", "norm4", false, M_DOWN, S4, T8, NO},             DGR_BLOCK("block4", T8, Y8, S8),
+    {"conv4_tr", "norm4_tr", false, M_UP, S8, U4, NO},         DGR_BLOCK("block4_tr", U4, V4, S4T),
+    {"conv3_tr", "norm3_tr", false, M_UP, CAT4, U2, NO},       DGR_BLOCK("block3_tr", U2, V2, S2T),
+    {"conv2_tr", "norm2_tr", false, M_UP, CAT2, U1, NO},       DGR_BLOCK("block2_tr", U1, V1, S1T),
+    {"conv1_tr", nullptr, false, M_IDENT, CAT1, H, NO},        // no bias, no BN: residual_block.py:38-44
+    {"final", nullptr, true, M_IDENT, H, OUT, NO}};            // the only bias: resunet.py:589-596
+#undef DGR_BLOCK
+constexpr int N_LAYERS = sizeof(LAYERS) / sizeof(LAYERS[0]);
+static_assert(N_LAYERS == 23, "ResUNetBN2C has 23 convs");
+
+// Which kernel runs a layer (layer_kind, the one place that decides it)
+enum Kind : int {
+  K_NONE,         // no forward yet
+  K_CONV1_FUSED,  // conv1 fused with its neighbour search (dgr_conv1_probe)
+  K_SMALL_CIN,    // conv1 with Cin <= 8, output-stationary over the rule-major map (conv.hip)
+  K_RULE,         // rule-major f32 product rows + reduction (conv.hip)
+  K_WIDE,         // rule-major product rows from split rows, f16x2 (conv_wide.hip) + reduction
+  K_OS_F32,       // output-stationary over neighbour tables, list-based, f32 operands (conv_os.hip)
+  K_OS,           // the same with split operands
+  K_DENSE,        // dense tiles (conv_dense.hip)
+  K_UP,           // transposed conv by parity class (conv_up.hip)
+  K_IDENTITY};    // kernel volume 1 (conv.hip)
+static bool on_tables(Kind k) { return k == K_OS_F32 || k == K_OS || k == K_DENSE || k == K_UP; }
+static bool reads_amax(Kind k) { return k == K_OS || k == K_DENSE || k == K_UP; }
+static bool writes_amax(Kind k) { return k == K_CONV1_FUSED || on_tables(k); }   // (their epilogues can)
+static bool rule_major(Kind k) { return k == K_RULE || k == K_WIDE; }   // product rows + the reduction: it alone can write split rows
 
 struct DgrLayer {
   std::string name;
@@ -42,43 +105,49 @@ struct DgrLayer {
   float *shift = nullptr;  // [cout] or nullptr
 };
 
-struct LayerRun {  // bookkeeping of the last forward, for dgr_net_layer_stats / dgr_net_rerun_layer
-  const int32_t *rule_ptr = nullptr;
+// One layer of the last forward as it was launched: what dgr_net_rerun_layer replays and dgr_net_layer_stats counts
+struct LayerRun {
+  Kind kind = K_NONE;
   const int32_t *n_in = nullptr, *n_out = nullptr;
-  int K = 1;
-  DgrConvLaunch launch;   // the exact launch of phase 1
-  DgrSplitRows split_in, split_out;   // wide-layer kernel: the input as split rows; what the reduction also writes
-  int out_relu = 0;
-  bool split_only = false;
-  bool small_cin = false;  // conv1 ran through the output-stationary kernel instead
-  const int32_t *fused_pairs = nullptr;  // conv1 fused with its neighbour search: device pair counter
-  bool os = false;                       // ran through the output-stationary kernel
-  DgrConvOsLaunch os_launch;
-  DgrNbrTable nbr;
-  DgrKernelMap km;  // copy (the map set itself lives on the forward's stack)
-  bool has_reduce = false;  // phase 2 parameters
-  const int32_t *red_ptr = nullptr, *red_pos = nullptr;
   int64_t n_out_cap = 0;
+  int K = 1;
+  DgrConvLaunch launch;   // phase 1 of K_RULE / K_WIDE / K_IDENTITY; the tensors of K_SMALL_CIN and K_CONV1_FUSED
+  DgrSplitRows split_in;  // K_WIDE: the input as split rows
+  DgrKernelMap km;        // K_SMALL_CIN: its map (copies: the map set itself lives on the forward's stack)
+  DgrConvOsLaunch os;     // the kinds on neighbour tables ...
+  DgrNbrTable nbr;        // ... and their table (os.nbr points here)
+  DgrCoordMap cm0;        // K_CONV1_FUSED: the coordinate map it searches, its device pair counter, the row maxima it leaves
+  int32_t *fused_pairs = nullptr;
+  uint32_t *fused_amax = nullptr;
+  const int32_t *rule_ptr = nullptr;   // the kinds on pair lists: pairs per offset (dgr_net_layer_stats)
+  // phase 2 of K_RULE / K_WIDE: the reduction
+  const int32_t *red_ptr = nullptr, *red_pos = nullptr;
   const float *res = nullptr;
-  int res_ld = 0, res_relu = 0;
+  int res_ld = 0, res_relu = 0, out_relu = 0;
+  DgrSplitRows split_out;   // what the reduction also writes
+  bool split_only = false;  // ... and the only thing
 };
 
-struct DgrTensorRef {
-  const float *ptr = nullptr;
-  int ld = 0, cols = 0;
-  const int32_t *n_dev = nullptr;
-  const int32_t *canon = nullptr;   // rows of a coarse 6-D map: library numbering -> first-occurrence numbering
-};
-
-// One named tensor of the last forward in every representation it has (dgr_net_get_tensor): null = not written
-struct DgrTensorRec {
-  const float *f32 = nullptr;            // signed f32 rows (row stride ld)
-  int ld = 0, cols = 0;
-  const uint32_t *amax = nullptr;        // 3-D net: per row the bits of its largest |x| after the pending ReLU
-  const unsigned char *planes = nullptr; // 6-D net: split rows, 4 * cols bytes per row ...
-  const float *scale = nullptr;          // ... and their per-row scale
-  const unsigned char *dsplit = nullptr; // 3-D net: dense split rows, 4 * cols bytes per row
-  const int32_t *n_dev = nullptr, *canon = nullptr;
+// One tensor of a forward in every form it has
+struct Tensor {
+  float *ptr = nullptr;
+  int ld = 0;
+  int relu = 0;  // consumers must apply ReLU when reading
+  DgrSplitRows split;   // set for tensors a wide layer gathers: written by the tensor's producer (ReLU applied)
+  bool split_only = false;   // ... and nobody reads the f32 rows (a block's middle tensor): they are not written
+  // 3-D net: per row the bits of its largest |x| (after the pending ReLU), left behind by the tensor's producer for the
+  // split-operand consumers (conv_os.hip / conv_dense.hip); amax2: the same array of the concatenation this tensor is a
+  // column range of.  Zero-initialised, filled by atomicMax.
+  uint32_t *amax = nullptr, *amax2 = nullptr;
+  // 3-D net: the rows as ready-made operand pieces of the dense-tile kernel (conv_dense.hip, "dense split rows": 4 x
+  // channels bytes per row), written by the tensor's producer; dsplit_only: nobody reads the f32 rows (a block's middle
+  // tensor) -- they are not written and `dsplit` is the tensor's own buffer
+  unsigned char *dsplit = nullptr;
+  bool dsplit_only = false;
+  // 3-D net, tensors between the output-stationary kernels and the wide rule-major layers of the coarse levels: the
+  // producer could not leave the representation the consumer reads, so the consumer's launch makes it first --
+  // split_pending: `split` from the f32 rows (dgr_split_rows); amax_pending: `amax` from the f32 rows (dgr_row_amax)
+  bool split_pending = false, amax_pending = false;
 };
 
 // The immutable half of a net: the folded, re-tiled weights in HBM.  Shared (reference-counted) by every dgr_net made
@@ -111,10 +180,11 @@ struct dgr_net {
   dgr_ctx *ctx;
   int D, cin, cout, conv1_ks, normalize;
   std::shared_ptr<DgrWeights> W;
-  LayerRun runs[23];
-  std::map<std::string, DgrTensorRef> inter;
-  std::map<std::string, DgrTensorRec> tensors;
-  uint64_t run_generation = 0;   // arena generation `runs` / `inter` point into
+  LayerRun runs[N_LAYERS];
+  Tensor tensors[N_TENSORS];     // by Tn: every tensor in the forms the last forward really wrote (dgr_net_get_tensor)
+  DgrCoordMap levels[4];         // ... and their coordinate maps (row counts, row numbering)
+  uint64_t run_generation = 0;   // arena generation `runs` / `tensors` point into
+  int width(Tn t) const { return TENSORS[t].cols == W_CIN ? cin : TENSORS[t].cols == W_COUT ? cout : TENSORS[t].cols; }
   // 3-D net on neighbour tables: the 128 / 256-channel layers of the two coarse levels run on the wide rule-major kernel
   // (dgr_net_set_wide_coarse; off: every K = 27 layer output-stationary, with row maxima behind every tensor)
   bool wide_coarse = false;
@@ -173,8 +243,11 @@ struct WeightPrep {
   }
 };
 
-static int make_layer(dgr_net *net, WeightPrep &P, const dgr_weight_desc *descs, int nd, const std::string &name, int K,
-                      int cin, int cout, const char *bn, bool bias) {
+static int make_layer(dgr_net *net, WeightPrep &P, const dgr_weight_desc *descs, int nd, const LayerRow &row, int K) {
+  const std::string name = row.name;
+  const char *bn = row.norm;
+  const bool bias = row.bias;
+  const int cin = net->width(row.in), cout = net->width(row.out);
   DgrLayer L;
   L.name = name;
   L.K = K; L.cin = cin; L.cout = cout;
@@ -266,8 +339,8 @@ static int make_layer(dgr_net *net, WeightPrep &P, const dgr_weight_desc *descs,
   const bool use_wide = K > 1 && !dgr_exact_f32() && dgr_conv_wide_supported(L.cin_pad, cin, cout) && !(net->D == 3 && K == 27);
   // 3-D nets that run on neighbour tables: the same-stride and strided (not the transposed) 128 / 256-channel layers of
   // the two coarse levels ALSO get the wide kernel's operands -- they run on it over lists derived from the tables
-  // (Fwd::conv), next to the w16 / w16b copies of the output-stationary kernel, which DGR_NO_WIDE3=1 still selects
-  const bool transposed = name.size() > 3 && name.compare(name.size() - 3, 3, "_tr") == 0;
+  // (layer_kind), next to the w16 / w16b copies of the output-stationary kernel, which DGR_NO_WIDE3=1 still selects
+  const bool transposed = row.map == M_UP;
   const bool wide3 = net->D == 3 && K == 27 && net->cin <= 8 && net->conv1_ks <= 7 && !transposed && !dgr_exact_f32() &&
                      cin >= 128 && cout >= 128 && dgr_conv_wide_supported(L.cin_pad, cin, cout);
   if (use_wide || wide3) {
@@ -422,22 +495,8 @@ static int net_create(dgr_ctx *ctx, int D, int in_channels, int out_channels, in
   int k3 = 1, k1 = 1;
   for (int d = 0; d < D; ++d) { k3 *= 3; k1 *= conv1_kernel_size; }
   int rc = DGR_OK;
-  auto L = [&](const std::string &name, int K, int ci, int co, const char *bn, bool bias = false) {
-    if (rc == DGR_OK) rc = make_layer(net, P, weights, n_weights, name, K, ci, co, bn, bias);
-  };
-  auto block = [&](const std::string &b, int c) {
-    L(b + ".conv1", k3, c, c, (b + ".norm1").c_str());
-    L(b + ".conv2", k3, c, c, (b + ".norm2").c_str());
-  };
-  L("conv1", k1, in_channels, CH[1], "norm1");          block("block1", CH[1]);
-  L("conv2", k3, CH[1], CH[2], "norm2");                block("block2", CH[2]);
-  L("conv3", k3, CH[2], CH[3], "norm3");                block("block3", CH[3]);
-  L("conv4", k3, CH[3], CH[4], "norm4");                block("block4", CH[4]);
-  L("conv4_tr", k3, CH[4], TR[4], "norm4_tr");          block("block4_tr", TR[4]);
-  L("conv3_tr", k3, CH[3] + TR[4], TR[3], "norm3_tr");  block("block3_tr", TR[3]);
-  L("conv2_tr", k3, CH[2] + TR[3], TR[2], "norm2_tr");  block("block2_tr", TR[2]);
-  L("conv1_tr", 1, CH[1] + TR[2], TR[1], nullptr);      // no bias, no BN: residual_block.py:38-44
-  L("final", 1, TR[1], out_channels, nullptr, true);    // the only bias: resunet.py:589-596
+  for (const LayerRow &row : LAYERS)
+    if (rc == DGR_OK) rc = make_layer(net, P, weights, n_weights, row, row.map == M_CONV1 ? k1 : row.map == M_IDENT ? 1 : k3);
   // the caller may free its tensors when the call returns
   if (rc == DGR_OK) rc = [&] { DGR_HIP_CHECK(hipStreamSynchronize(P.s)); return DGR_OK; }();
   if (rc != DGR_OK) {
@@ -493,26 +552,104 @@ extern "C" int dgr_net_num_layers(const dgr_net *net) { return net ? (int)net->W
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
-struct Tensor {
-  float *ptr;
-  int ld;
-  int relu;  // consumers must apply ReLU when reading
-  DgrSplitRows split;   // set for tensors a wide layer gathers: written by the tensor's producer (ReLU applied)
-  bool split_only = false;   // ... and nobody reads the f32 rows (a block's middle tensor): they are not written
-  // 3-D net: per row the bits of its largest |x| (after the pending ReLU), left behind by the tensor's producer for the
-  // split-operand consumers (conv_os.hip / conv_dense.hip); amax2: the same array of the concatenation this tensor is a
-  // column range of.  Zero-initialised, filled by atomicMax.
-  uint32_t *amax = nullptr, *amax2 = nullptr;
-  // 3-D net: the rows as ready-made operand pieces of the dense-tile kernel (conv_dense.hip, "dense split rows": 4 x
-  // channels bytes per row), written by the tensor's producer; dsplit_only: nobody reads the f32 rows (a block's middle
-  // tensor) -- they are not written and `dsplit` is the tensor's own buffer
-  unsigned char *dsplit = nullptr;
-  bool dsplit_only = false;
-  // 3-D net, tensors between the output-stationary kernels and the wide rule-major layers of the coarse levels: the
-  // producer could not leave the representation the consumer reads, so the consumer's launch makes it first --
-  // split_pending: `split` from the f32 rows (dgr_split_rows); amax_pending: `amax` from the f32 rows (dgr_row_amax)
-  bool split_pending = false, amax_pending = false;
-};
+// ---- which kernel runs which layer: decided here and nowhere else
+// The forward's environment switches, read once per process (the tests run the switched variants as references):
+// DGR_OS_LISTS: every layer on neighbour tables through the list-based kernel (A/B + the bit-identity test of the
+// kernels); DGR_NO_WIDE3: dgr_net_set_wide_coarse has no effect; DGR_NO_DSPLIT: a residual block's middle tensor stays f32.
+struct Switches { bool os_lists, no_wide3, no_dsplit; };
+static const Switches &switches() {
+  static const Switches s{getenv("DGR_OS_LISTS") != nullptr, getenv("DGR_NO_WIDE3") != nullptr, getenv("DGR_NO_DSPLIT") != nullptr};
+  return s;
+}
+
+// A layer's kernel map in both forms, as its LayerRow::map names it
+struct MapRef { Map map; const DgrKernelMap *km; const DgrNbrTable *nbr; bool swapped; };
+static MapRef map_of(const DgrMapSet &ms, Map map, int lvl_in, int lvl_out) {
+  switch (map) {
+    case M_CONV1: return {map, &ms.conv1, nullptr, false};
+    case M_SAME: return {map, &ms.same[lvl_in], &ms.nsame[lvl_in], false};
+    case M_DOWN: return {map, &ms.down[lvl_in], &ms.ndown[lvl_in], false};
+    case M_UP: return {map, &ms.down[lvl_out], &ms.nup[lvl_out], true};   // the strided map with in / out swapped
+    default: return {map, nullptr, nullptr, false};
+  }
+}
+
+// The mode of a forward, needed before its maps exist.  With dgr_net_set_wide_coarse the 128 / 256-channel layers of the
+// two coarse levels of a 3-D net on neighbour tables run on the wide rule-major kernel over lists derived from the tables
+// (DGR_NO_WIDE3=1 / DGR_OS_LISTS=1: on the output-stationary kernel after all).  Their product rows are reserved by the
+// host's bound of 27 pairs per INPUT voxel (the coarse levels' row counts live on the device): 27 KB per voxel --
+// forwards beyond 16 GB of that stay on the output-stationary kernel.
+static bool wide_coarse_mode(const dgr_net *net, bool use_nbr, int64_t N) {
+  const std::vector<DgrLayer> &Ls = net->W->layers;
+  return net->wide_coarse && use_nbr && !switches().no_wide3 && !switches().os_lists && !dgr_exact_f32() &&
+         std::any_of(Ls.begin(), Ls.end(), [](const DgrLayer &L) { return L.wb != nullptr; }) &&
+         27 * N * 256 * (int64_t)sizeof(float) <= (16ll << 30);
+}
+
+// ... and the kernel of one layer, once the maps are built: `in_ld` = row stride of its input, of at most n_in_cap rows
+static Kind layer_kind(const DgrMapSet &ms, bool wide3, const DgrLayer &L, const MapRef &m, bool has_res, int64_t n_in_cap,
+                       int in_ld) {
+  if (m.map == M_IDENT) return K_IDENTITY;
+  // FCGF conv1 (ks^3 offsets, <= 8 input channels) is fused with its neighbour search: no map for it
+  if (m.map == M_CONV1 && ms.use_nbr) return K_CONV1_FUSED;
+  // 3-D net on neighbour tables; in wide-coarse mode the layers with wide-kernel weights run rule-major over the tables' lists
+  if (ms.use_nbr && !(wide3 && L.wb && !m.swapped && m.km->built)) {
+    const bool split = L.w16b && !dgr_exact_f32();
+    // dense tiles and parity classes read operand pieces straight from memory, by buffer loads that address the input
+    // with 32-bit byte offsets: tensors of 2 GB and more stay on the list kernel
+    const bool tiles = split && L.w16d && !switches().os_lists && dgr_fits_32bit_offsets(n_in_cap, in_ld);
+    // same-stride layers with C <= 64 (the two finest levels of ResUNetBN2C): dense tiles, no pair lists
+    if (tiles && m.map == M_SAME && dgr_conv_dense_supported(L.cin, L.cin_pad, L.cout)) return K_DENSE;
+    // transposed convs with Cin, Cout multiples of 64: by parity class of the output rows
+    if (tiles && m.map == M_UP && m.nbr->perm && !has_res && dgr_conv_up_supported(L.cin, L.cin_pad, L.cout)) return K_UP;
+    return split ? K_OS : K_OS_F32;
+  }
+  // (Cin = 6 / 1 -- the inlier net's two input widths -- run the thread-per-voxel variant, conv.hip)
+  if (!m.swapped && !has_res && L.cin <= 8 && L.cout == 32 && L.cin_pad == 8) return K_SMALL_CIN;
+  return L.wb ? K_WIDE : K_RULE;
+}
+
+// Rows per workgroup and input channels per pipeline phase of the list-based output-stationary kernel, measured per layer
+// shape on the benchmark's clouds (tools/r06_runs/run15-17.sh): the coarse levels have few rows and need small blocks to
+// fill 256 CUs; with Cin >= 128 a phase of 128 channels halves the number of barrier-separated phases per tile, and at
+// level 2 that pays for 64-row blocks (half the weight fragments through the vector-memory path); the one wide layer
+// that writes level 0 (conv2_tr) is faster with 64
+static int os_rows_per_block(int cin_pad, int lvl_out) { return lvl_out <= 1 ? 64 : lvl_out == 2 ? (cin_pad >= 128 ? 64 : 32) : 16; }
+static int os_phase_channels(int cin_pad, int lvl_out) { return (cin_pad >= 256 || (cin_pad == 128 && lvl_out >= 2)) ? 128 : 64; }
+
+// One recorded layer, launched: phase 1, `mid` (nullable) recorded behind it, phase 2 where the kind has one.  The
+// forward and dgr_net_rerun_layer both launch through here.  clk: K_WIDE stamps its own start / end there (profiling).
+static int run_layer(dgr_ctx *ctx, const dgr_net *net, int li, hipStream_t stream, hipEvent_t mid,
+                     const char **kname = nullptr, unsigned long long *clk = nullptr) {
+  const DgrLayer &L = net->W->layers[li];
+  const LayerRun &r = net->runs[li];
+  const DgrConvLaunch &a = r.launch;
+  switch (r.kind) {
+    case K_CONV1_FUSED:   // (allocates its search's temporaries: the one kind that cannot be replayed)
+      DGR_CHECK(dgr_conv1_probe(ctx->arena, r.cm0, net->conv1_ks, a.in, a.in_ld, L.cin, L.w, L.shift, a.out, a.out_ld,
+                                r.fused_pairs, stream, L.wc, kname, r.fused_amax));
+      break;
+    case K_SMALL_CIN:
+      DGR_CHECK(dgr_conv_small_cin(a.in, a.in_ld, a.in_relu, L.cin, L.w, L.wq, L.shift, r.km, r.n_out, r.n_out_cap, a.out,
+                                   a.out_ld, stream));
+      break;
+    case K_WIDE: {
+      DgrConvLaunch ac = a;
+      ac.clk = clk;
+      DGR_CHECK(dgr_conv_wide_launch(ac, r.split_in, L.wb, L.wb_piece, L.w_unscale, ctx->num_cus, stream, kname));
+      break;
+    }
+    case K_RULE: case K_IDENTITY: DGR_CHECK(dgr_conv_launch(a, ctx->num_cus, stream, kname)); break;
+    case K_OS_F32: case K_OS: case K_DENSE: case K_UP: DGR_CHECK(dgr_conv_os_launch(r.os, stream, kname)); break;
+    default: DGR_REQUIRE(false, "layer %s: not launched yet", L.name.c_str());
+  }
+  if (mid) DGR_HIP_CHECK(hipEventRecord(mid, stream));   // end of the MFMA phase
+  if (rule_major(r.kind))
+    DGR_CHECK(dgr_reduce_rows(a.y, L.cout, r.red_ptr, r.red_pos, r.n_out, r.n_out_cap, r.split_only ? nullptr : a.out, a.out_ld,
+                              L.shift, r.res, r.res_ld, r.res_relu, stream, r.split_out.planes ? &r.split_out : nullptr,
+                              r.out_relu));
+  return DGR_OK;
+}
 
 struct Fwd {
   dgr_ctx *ctx;
@@ -520,151 +657,109 @@ struct Fwd {
   hipStream_t stream;
   DgrMapSet ms;
   bool prof;
-  bool l2_next = false;   // the next identity-map conv writes unit-norm rows (the `final` conv of a normalising net)
-  bool wide3 = false;     // 3-D net on neighbour tables: layers with wide-kernel weights run rule-major over the tables' lists
-
+  bool wide3 = false;     // wide_coarse_mode
   float *ybuf = nullptr;  // per-pair product rows, sized for the largest layer of this forward
 
-  // one conv: Y[pair] = in[pair_in] W[k] (MFMA), then out[o] = shift (+res) + sum of the row's Y rows
-  int conv(int li, const Tensor &in, const DgrKernelMap *km, bool swapped, int lvl_in, int lvl_out,
-           const Tensor &out, const Tensor *res) {
+  // One conv through kernel `kind`: fills the layer's run record, makes the pending forms of its input, launches the
+  // record.  Rule-major kinds: Y[pair] = in[pair_in] W[k] (MFMA), then out[o] = shift (+res) + sum of the row's Y rows.
+  int conv(int li, Kind kind, const Tensor &in, const MapRef &m, int lvl_in, int lvl_out, const Tensor &out, const Tensor *res,
+           bool l2_normalize) {
     const DgrLayer &L = net->W->layers[li];
     const DgrCoordMap &cin_map = ms.cm[lvl_in], &cout_map = ms.cm[lvl_out];
-    DgrConvLaunch a;
+    const DgrKernelMap *km = m.km;
+    LayerRun &r = net->runs[li];
+    r = LayerRun();
+    r.kind = kind;
+    r.n_in = cin_map.n_dev; r.n_out = cout_map.n_dev; r.n_out_cap = cout_map.n_cap;
+    r.K = L.K;
+    DgrConvLaunch &a = r.launch;
     a.in = in.ptr; a.in_ld = in.ld; a.in_relu = in.relu;
     a.out = out.ptr; a.out_ld = out.ld;
     a.y = ybuf; a.shift = L.shift;
     a.w = L.w;
     a.cin = L.cin; a.cin_pad = L.cin_pad; a.cout = L.cout; a.cout_pad = L.cout_pad; a.K = L.K;
-    const bool wide3_layer = wide3 && km && ms.use_nbr && L.wb && !swapped && km->built;
-    if (km && ms.use_nbr && !wide3_layer) {
-      a.pair_in = a.pair_out = a.tile_ptr = a.rule_ptr = nullptr;   // output-stationary path below
-      a.tile_desc = nullptr; a.n_rows_dev = nullptr; a.tile_bound = 0;
-    } else if (km) {
-      a.pair_in = swapped ? km->pair_out : km->pair_in;
-      a.pair_out = swapped ? km->pair_in : km->pair_out;
-      a.tile_ptr = km->tile_ptr; a.rule_ptr = km->rule_ptr; a.tile_desc = km->tile_desc;
-      a.n_rows_dev = nullptr;
-      a.tile_bound = km->pair_cap / DGR_TILE_M + km->K;
-      DGR_REQUIRE(km->K == L.K, "layer %s: kernel volume mismatch", L.name.c_str());
-      DGR_REQUIRE(!swapped || km->in_ptr, "layer %s: map has no in-major CSR", L.name.c_str());
-    } else {
-      DGR_REQUIRE(res == nullptr, "identity conv with residual not supported");
-      a.pair_in = a.pair_out = a.tile_ptr = a.rule_ptr = nullptr;
-      a.tile_desc = nullptr;
-      a.n_rows_dev = cout_map.n_dev;
-      a.tile_bound = dgr_ceil_div(cout_map.n_cap, DGR_TILE_M);
-      a.l2_normalize = l2_next ? 1 : 0;
-      l2_next = false;
-    }
-    hipEvent_t e0 = nullptr, em = nullptr, e1 = nullptr;
-    if (prof) {
-      e0 = ctx->events.next(); em = ctx->events.next(); e1 = ctx->events.next();
-      if (!e0 || !em || !e1) return DGR_EHIP;
-      DGR_HIP_CHECK(hipEventRecord(e0, stream));
-    }
-    if (km && ms.use_nbr && !wide3_layer) {
+    a.pair_in = a.pair_out = a.tile_ptr = a.rule_ptr = nullptr;
+    a.tile_desc = nullptr; a.n_rows_dev = nullptr; a.tile_bound = 0;
+    DGR_REQUIRE(!out.split.planes || out.split_pending || rule_major(kind), "layer %s: only a reduction can write split rows",
+                L.name.c_str());
+    DGR_REQUIRE(kind == K_DENSE || (!in.dsplit_only && !out.dsplit_only), "layer %s: dense split rows outside the dense-tile kernel", L.name.c_str());
+    // the default names: of the kinds whose launch reports none of its own
+    const char *kname = (L.cin == 6 && L.wq) ? "conv_cin6_quad_kernel" : L.cin == 1 ? "conv_small_cin_row_kernel" : "conv_small_cin_kernel";
+    if (kind == K_CONV1_FUSED) {
+      kname = "conv1_grid_kernel";
+      r.cm0 = cin_map;
+      DGR_ALLOC(r.fused_pairs, ctx->arena, int32_t, 1);
+      r.fused_amax = out.amax;
+    } else if (on_tables(kind)) {
       // D = 3: output-stationary fused conv over the dense neighbour table of this (in map, out map) pair
-      const DgrNbrTable *t = nullptr;
-      for (int l = 0; l < 4; ++l)
-        if (km == &ms.same[l]) t = &ms.nsame[l];
-      for (int l = 0; l < 3; ++l)
-        if (km == &ms.down[l]) t = swapped ? &ms.nup[l] : &ms.ndown[l];
-      DGR_REQUIRE(t && t->built && L.w16, "layer %s: no neighbour table / 16x16 weights", L.name.c_str());
-      DgrConvOsLaunch o;
+      kname = "sparse_conv_os";
+      DGR_REQUIRE(m.nbr && m.nbr->built && L.w16, "layer %s: no neighbour table / 16x16 weights", L.name.c_str());
+      DgrConvOsLaunch &o = r.os;
       o.in = in.ptr; o.in_ld = in.ld; o.in_relu = in.relu;
       o.out = out.ptr; o.out_ld = out.ld; o.out_relu = out.relu;
-      // rows per workgroup and input channels per pipeline phase of the list-based kernel, measured per layer shape on
-      // the benchmark's clouds (tools/r06_runs/run15-17.sh): the coarse levels have few rows and need small blocks to fill
-      // 256 CUs; with Cin >= 128 a phase of 128 channels halves the number of barrier-separated phases per tile, and at
-      // level 2 that pays for 64-row blocks (half the weight fragments through the vector-memory path); the one wide layer
-      // that writes level 0 (conv2_tr) is faster with 64
-      o.rows_per_block = lvl_out <= 1 ? 64 : lvl_out == 2 ? (L.cin_pad >= 128 ? 64 : 32) : 16;
-      o.phase_channels = (L.cin_pad >= 256 || (L.cin_pad == 128 && lvl_out >= 2)) ? 128 : 64;
-      if (const char *e = getenv(lvl_out == 2 ? "DGR_OS_MB2" : lvl_out == 3 ? "DGR_OS_MB3" : "DGR_OS_MB01")) o.rows_per_block = atoi(e);
-      if (const char *e = getenv("DGR_OS_CK")) o.phase_channels = atoi(e);
+      o.rows_per_block = os_rows_per_block(L.cin_pad, lvl_out);
+      o.phase_channels = os_phase_channels(L.cin_pad, lvl_out);
       o.w16 = L.w16; o.shift = L.shift;
       o.wb3 = L.w16b; o.piece_stride = L.w16b_piece;
       o.wbd = L.w16d;
       o.w_unscale = L.w_unscale; o.n_in_cap = cin_map.n_cap;
-      if (L.w16b && !dgr_exact_f32()) {
+      if (reads_amax(kind)) {
+        DGR_REQUIRE(in.amax, "layer %s: the split-operand kernels need the input rows' maxima", L.name.c_str());
         o.row_amax = in.amax;
-        if (in.amax && in.amax_pending)   // the rows came out of a reduction, which leaves no row maxima behind
-          DGR_CHECK(dgr_row_amax(in.ptr, in.ld, L.cin, in.relu, cin_map.n_dev, cin_map.n_cap, in.amax, stream));
-        if (!o.row_amax) {   // a tensor that did not come out of one of the conv kernels (the single-layer debug entry)
-          uint32_t *mx;
-          DGR_ALLOC(mx, ctx->arena, uint32_t, cin_map.n_cap);
-          DGR_CHECK(dgr_row_amax(in.ptr, in.ld, L.cin, in.relu, cin_map.n_dev, cin_map.n_cap, mx, stream));
-          o.row_amax = mx;
-        }
       }
       o.out_amax = out.amax; o.out_amax2 = out.amax2;
       o.res = res ? res->ptr : nullptr; o.res_ld = res ? res->ld : 0; o.res_relu = res ? res->relu : 0;
-      o.nbr = t; o.n_out_dev = cout_map.n_dev; o.n_out_cap = cout_map.n_cap;
+      r.nbr = *m.nbr;
+      o.nbr = &r.nbr; o.n_out_dev = cout_map.n_dev; o.n_out_cap = cout_map.n_cap;
       o.cin = L.cin; o.cin_pad = L.cin_pad; o.cout = L.cout;
-      // same-stride layers with C <= 64 (the two finest levels of ResUNetBN2C): dense tiles, no pair lists
-      static const bool os_lists = getenv("DGR_OS_LISTS") != nullptr;   // A/B + the bit-identity test of the two kernels
-      bool same_stride = false;
-      for (int l = 0; l < 4; ++l) same_stride = same_stride || t == &ms.nsame[l];
-      // (its buffer loads address the input with 32-bit byte offsets: tensors of 2 GB and more stay on the list kernel)
-      o.dense = same_stride && o.row_amax && o.wbd && !os_lists && dgr_conv_dense_supported(L.cin, L.cin_pad, L.cout) &&
-                dgr_fits_32bit_offsets(cin_map.n_cap, in.ld);
-      DGR_REQUIRE(o.dense || (!in.dsplit_only && !out.dsplit_only), "layer %s: dense split rows outside the dense-tile kernel", L.name.c_str());
-      // transposed convs (the strided map used swapped) with Cin, Cout multiples of 64: by parity class of the output rows
-      static const bool no_up = getenv("DGR_NO_UP") != nullptr;   // A/B
-      o.up = swapped && !o.dense && !no_up && !os_lists && o.row_amax && o.wbd && t->perm && res == nullptr &&
-             dgr_conv_up_supported(L.cin, L.cin_pad, L.cout) && dgr_fits_32bit_offsets(cin_map.n_cap, in.ld);
+      o.dense = kind == K_DENSE;
+      o.up = kind == K_UP;
       if (o.dense) {
         o.in_dsplit = in.dsplit;
         o.out_dsplit = out.dsplit;
         if (out.dsplit_only) o.out = nullptr;
       }
-      const char *kname = "sparse_conv_os";
-      DGR_CHECK(dgr_conv_os_launch(o, stream, &kname));
-      if (prof) {
-        DGR_HIP_CHECK(hipEventRecord(e1, stream));
-        ctx->conv_spans.push_back({e0, e1});
-        ctx->gemm_spans.push_back({e0, e1});
-        ctx->conv_kinds.push_back(kname);
-      }
-      LayerRun &r = net->runs[li];
-      r = LayerRun();
-      r.os = true;
-      r.os_launch = o;
-      r.nbr = *t;
-      r.os_launch.nbr = &r.nbr;
-      r.n_in = cin_map.n_dev; r.n_out = cout_map.n_dev; r.K = L.K;
-      r.n_out_cap = cout_map.n_cap;
-      return DGR_OK;
+    } else if (kind == K_IDENTITY) {
+      DGR_REQUIRE(res == nullptr, "identity conv with residual not supported");
+      a.n_rows_dev = cout_map.n_dev;
+      a.tile_bound = dgr_ceil_div(cout_map.n_cap, DGR_TILE_M);
+      a.l2_normalize = l2_normalize ? 1 : 0;
+    } else {
+      a.pair_in = m.swapped ? km->pair_out : km->pair_in;
+      a.pair_out = m.swapped ? km->pair_in : km->pair_out;
+      a.tile_ptr = km->tile_ptr; a.rule_ptr = km->rule_ptr; a.tile_desc = km->tile_desc;
+      a.tile_bound = km->pair_cap / DGR_TILE_M + km->K;
+      DGR_REQUIRE(km->K == L.K, "layer %s: kernel volume mismatch", L.name.c_str());
+      DGR_REQUIRE(!m.swapped || km->in_ptr, "layer %s: map has no in-major CSR", L.name.c_str());
+      DGR_REQUIRE(kind != K_WIDE || in.split.planes, "layer %s: the wide-layer kernel needs its input as split rows", L.name.c_str());
+      r.km = *km;
+      r.rule_ptr = km->rule_ptr;
+      r.split_in = kind == K_WIDE ? in.split : DgrSplitRows();
+      r.red_ptr = m.swapped ? km->in_ptr : km->out_ptr;
+      r.red_pos = m.swapped ? km->in_pos : km->out_pos;
+      r.res = res ? res->ptr : nullptr; r.res_ld = res ? res->ld : 0; r.res_relu = res ? res->relu : 0;
+      r.split_out = out.split;
+      r.split_only = out.split_only;
+      r.out_relu = out.relu;
     }
-    const bool small_cin = km && !swapped && !res && L.cin <= 8 && L.cout == 32 && L.cin_pad == 8;
-    // (Cin = 6 / 1 -- the inlier net's two input widths -- run the thread-per-voxel variant, conv.hip)
-    const char *kname = (L.cin == 6 && L.wq) ? "conv_cin6_quad_kernel" : L.cin == 1 ? "conv_small_cin_row_kernel" : "conv_small_cin_kernel";
+    hipEvent_t e0 = nullptr, em = nullptr, e1 = nullptr;
     unsigned long long *clk = nullptr;
-    const bool wide = L.wb && km;
-    if (small_cin)
-      DGR_CHECK(dgr_conv_small_cin(in.ptr, in.ld, in.relu, L.cin, L.w, L.wq, L.shift, *km, cout_map.n_dev, cout_map.n_cap,
-                                   out.ptr, out.ld, stream));
-    else if (wide) {
-      DGR_REQUIRE(in.split.planes, "layer %s: the wide-layer kernel needs its input as split rows", L.name.c_str());
-      if (in.split_pending)   // the rows came out of an output-stationary kernel, which writes f32 rows only
-        DGR_CHECK(dgr_split_rows(in.ptr, in.ld, in.relu, cin_map.n_dev, cin_map.n_cap, in.split, stream));
-      if (prof) {   // the kernel stamps its own start / end (dgr_ctx_conv_launch_kernel_us)
-        DGR_ALLOC(a.clk, ctx->arena, unsigned long long, 2);
-        DGR_HIP_CHECK(hipMemsetAsync(a.clk, 0xff, sizeof(unsigned long long), stream));       // start: atomicMin
-        DGR_HIP_CHECK(hipMemsetAsync(a.clk + 1, 0, sizeof(unsigned long long), stream));      // end: atomicMax
-        clk = a.clk;
-      }
-      DGR_CHECK(dgr_conv_wide_launch(a, in.split, L.wb, L.wb_piece, L.w_unscale, ctx->num_cus, stream, &kname));
-    } else
-      DGR_CHECK(dgr_conv_launch(a, ctx->num_cus, stream, &kname));
-    if (prof) DGR_HIP_CHECK(hipEventRecord(em, stream));   // end of the MFMA phase
-    DGR_REQUIRE(!out.split.planes || (km && !small_cin), "layer %s: only a reduction can write split rows", L.name.c_str());
-    if (km && !small_cin)
-      DGR_CHECK(dgr_reduce_rows(ybuf, L.cout, swapped ? km->in_ptr : km->out_ptr, swapped ? km->in_pos : km->out_pos,
-                                cout_map.n_dev, cout_map.n_cap, out.split_only ? nullptr : out.ptr, out.ld, L.shift, res ? res->ptr : nullptr,
-                                res ? res->ld : 0, res ? res->relu : 0, stream, out.split.planes ? &out.split : nullptr,
-                                out.relu));
+    if (prof) {
+      e0 = ctx->events.next(); em = ctx->events.next(); e1 = ctx->events.next();
+      if (!e0 || !em || !e1) return DGR_EHIP;
+      DGR_HIP_CHECK(hipEventRecord(e0, stream));
+    }
+    // the forms of the input that its producer could not leave, made in front of the launch (and not replayed with it)
+    if (reads_amax(kind) && in.amax_pending)   // (a reduction leaves no row maxima behind)
+      DGR_CHECK(dgr_row_amax(in.ptr, in.ld, L.cin, in.relu, cin_map.n_dev, cin_map.n_cap, in.amax, stream));
+    if (kind == K_WIDE && in.split_pending)    // (an output-stationary kernel writes f32 rows only)
+      DGR_CHECK(dgr_split_rows(in.ptr, in.ld, in.relu, cin_map.n_dev, cin_map.n_cap, in.split, stream));
+    if (prof && kind == K_WIDE) {   // the kernel stamps its own start / end (dgr_ctx_conv_launch_kernel_us)
+      DGR_ALLOC(clk, ctx->arena, unsigned long long, 2);
+      DGR_HIP_CHECK(hipMemsetAsync(clk, 0xff, sizeof(unsigned long long), stream));       // start: atomicMin
+      DGR_HIP_CHECK(hipMemsetAsync(clk + 1, 0, sizeof(unsigned long long), stream));      // end: atomicMax
+    }
+    DGR_CHECK(run_layer(ctx, net, li, stream, em, &kname, clk));
     if (prof) {
       DGR_HIP_CHECK(hipEventRecord(e1, stream));
       ctx->conv_spans.push_back({e0, e1});
@@ -673,27 +768,81 @@ struct Fwd {
       ctx->conv_clks.resize(ctx->conv_spans.size(), nullptr);
       ctx->conv_clks.back() = clk;
     }
-    LayerRun &r = net->runs[li];
-    a.clk = nullptr;   // (the recorded launch is re-run by dgr_net_rerun_layer after the arena moved on)
-    r.launch = a;
-    r.split_in = wide ? in.split : DgrSplitRows();
-    r.split_out = out.split;
-    r.out_relu = out.relu;
-    r.split_only = out.split_only;
-    r.has_reduce = km != nullptr;
-    r.small_cin = small_cin;
-    if (km) r.km = *km;
-    if (km) {
-      r.red_ptr = swapped ? km->in_ptr : km->out_ptr;
-      r.red_pos = swapped ? km->in_pos : km->out_pos;
-    }
-    r.n_out_cap = cout_map.n_cap;
-    r.res = res ? res->ptr : nullptr; r.res_ld = res ? res->ld : 0; r.res_relu = res ? res->relu : 0;
-    r.rule_ptr = km ? km->rule_ptr : nullptr;
-    r.n_in = cin_map.n_dev; r.n_out = cout_map.n_dev; r.K = L.K;
     return DGR_OK;
   }
 };
+
+// Which forms each tensor of a forward exists in, from the layer table and the layers' kinds: what its consumers read and
+// what its producer can leave behind.  Allocates them (the row maxima from ONE cleared allocation that the producers'
+// epilogues fill by atomicMax: round 3 ran a row-scale pass per consuming layer, 20 launches per forward).
+static int derive_forms(Fwd &f, const Kind kinds[N_LAYERS], Tensor t[N_TENSORS]) {
+  DgrArena &A = f.ctx->arena;
+  int producer[N_TENSORS], readers[N_TENSORS] = {};   // the layer that writes a tensor; how many read it, residuals included
+  std::fill(producer, producer + N_TENSORS, -1);
+  for (int li = 0; li < N_LAYERS; ++li) {
+    producer[LAYERS[li].out] = li;
+    readers[LAYERS[li].in]++;
+    if (LAYERS[li].res != NO) readers[LAYERS[li].res]++;
+  }
+  for (const auto &e : INTERMEDIATES) readers[e.t]++;   // (dgr_net_get_intermediate reads f32 rows)
+  bool want_amax[N_TENSORS] = {};
+  // whether everything that writes into tensor i -- its producer, or those of the halves of a concatenation -- is `can`
+  auto left_by = [&](int i, bool (*can)(Kind)) {
+    bool any = false, all = true;
+    for (int j = 0; j < N_TENSORS; ++j)
+      if (TENSORS[j].buf == TENSORS[i].buf && TENSORS[j].col0 >= TENSORS[i].col0 &&
+          TENSORS[j].col0 + TENSORS[j].cols <= TENSORS[i].col0 + TENSORS[i].cols && producer[j] >= 0) {
+        any = true;
+        all = all && can(kinds[producer[j]]);
+      }
+    return any && all;
+  };
+  int64_t amax_words = 0;
+  for (int li = 0; li < N_LAYERS; ++li) {
+    const int i = LAYERS[li].in;
+    const int64_t rows = f.ms.cm[TENSORS[i].lvl].n_cap;
+    const bool sole_reader = readers[i] == 1 && TENSORS[i].buf == i;   // not a residual, not half of a concatenation
+    // split rows: iff a consumer is the wide kernel; its producer's reduction writes them, and nothing else when that
+    // consumer is the only reader (the tensor between the two convs of a residual block)
+    if (kinds[li] == K_WIDE && !t[i].split.planes) {
+      t[i].split.channels = f.net->width((Tn)i);
+      DGR_ALLOC(t[i].split.planes, A, unsigned char, (size_t)rows * 4 * t[i].split.channels);
+      DGR_ALLOC(t[i].split.scale, A, float, rows);
+      t[i].split_pending = !left_by(i, rule_major);
+      t[i].split_only = sole_reader && !t[i].split_pending;
+    }
+    // row maxima: iff the layer is one of the kinds on neighbour tables or the producer's epilogue leaves them anyway;
+    // pending iff the consumer really reads them (split operands) and a producer cannot leave them
+    if (LAYERS[li].map != M_IDENT && (on_tables(kinds[li]) || left_by(i, writes_amax))) {
+      if (!want_amax[i]) amax_words += rows;
+      want_amax[i] = true;
+      t[i].amax_pending = t[i].amax_pending || (reads_amax(kinds[li]) && !left_by(i, writes_amax));
+    }
+    // dense split rows: the middle tensor of a residual block at the two finest levels goes from dense-tile kernel to
+    // dense-tile kernel: written as that kernel's operand pieces, and as nothing else
+    if (!switches().no_dsplit && sole_reader && kinds[li] == K_DENSE && producer[i] >= 0 && kinds[producer[i]] == K_DENSE &&
+        t[i].ld == f.net->width((Tn)i)) {
+      t[i].dsplit = reinterpret_cast<unsigned char *>(t[i].ptr);
+      t[i].dsplit_only = true;
+    }
+  }
+  if (amax_words) {
+    uint32_t *pool;
+    DGR_ALLOC(pool, A, uint32_t, amax_words);
+    DGR_HIP_CHECK(hipMemsetAsync(pool, 0, (size_t)amax_words * sizeof(uint32_t), f.stream));
+    for (int i = 0; i < N_TENSORS; ++i)
+      if (want_amax[i]) {
+        t[i].amax = pool;
+        pool += f.ms.cm[TENSORS[i].lvl].n_cap;
+      }
+    // both halves of a concatenation feed its row maxima, where their producers can
+    for (int i = 0; i < N_TENSORS; ++i) {
+      const Tn cat = TENSORS[i].buf;
+      if (cat != i && t[cat].amax && left_by(i, writes_amax)) t[i].amax2 = t[cat].amax;
+    }
+  }
+  return DGR_OK;
+}
 
 int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, const float *feats,
                              int64_t N, float *out, hipStream_t stream) {
@@ -710,211 +859,59 @@ int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, 
   // size <= 7, also 3); such a 3-D net needs no rule-major map at all: the K = 27 layers run output-stationary over
   // dense neighbour tables (conv_os.hip).  Any other 3-D shape takes the rule-major two-phase path of conv.hip.
   const bool use_nbr = net->D == 3 && net->cin <= 8 && net->conv1_ks <= 7;
-  const bool conv1_fused = use_nbr;
-  // With dgr_net_set_wide_coarse the 128 / 256-channel layers of the two coarse levels run on the wide rule-major kernel
-  // over lists derived from the tables (DGR_NO_WIDE3=1 / DGR_OS_LISTS=1: on the output-stationary kernel after all).  Their product rows
-  // are reserved by the host's bound of 27 pairs per INPUT voxel (the coarse levels' row counts live on the device):
-  // 27 KB per voxel -- forwards beyond 16 GB of that stay on the output-stationary kernel.
-  static const bool no_wide3 = getenv("DGR_NO_WIDE3") != nullptr || getenv("DGR_OS_LISTS") != nullptr;
-  f.wide3 = net->wide_coarse && use_nbr && !no_wide3 && !dgr_exact_f32() && net->W->layers[7].wb && 27 * N * 256 * (int64_t)sizeof(float) <= (16ll << 30);
-  DGR_CHECK(dgr_build_maps(A, coords, N, net->D, net->conv1_ks, &f.ms, stream, conv1_fused, /*lean=*/true, use_nbr, f.wide3));
+  f.wide3 = wide_coarse_mode(net, use_nbr, N);
+  DGR_CHECK(dgr_build_maps(A, coords, N, net->D, net->conv1_ks, &f.ms, stream, /*skip_conv1_map=*/use_nbr, /*lean=*/true, use_nbr, f.wide3));
   if (f.prof) {
     DGR_HIP_CHECK(hipEventRecord(m1, stream));
     (net->D == 3 ? ctx->map3_spans : ctx->map6_spans).push_back({m0, m1});
   }
+  const DgrMapSet &ms = f.ms;
+  Kind kinds[N_LAYERS];
+  MapRef maps[N_LAYERS];
   {
-    // Y capacity: the largest (pair capacity x Cout) over the layers of this net
-    const DgrMapSet &m = f.ms;
-    int64_t need = m.use_nbr ? 64 : m.conv1.pair_cap * 32;
-    const int64_t same_c[4] = {64, 64, 128, 256}, down_c[3] = {64, 128, 256};  // widest Cout per map
+    // Y capacity: the largest (pair capacity x Cout) over the layers of this net that leave product rows
     // (a 3-D net on neighbour tables has lists -- and product rows -- for the maps of its wide layers only)
-    for (int l = 0; l < 4; ++l) if (m.same[l].built) need = std::max(need, m.same[l].pair_cap * same_c[l]);
-    for (int l = 0; l < 3; ++l) if (m.down[l].built) need = std::max(need, m.down[l].pair_cap * down_c[l]);
+    int64_t need = 64;
+    for (int li = 0; li < N_LAYERS; ++li) {
+      const LayerRow &row = LAYERS[li];
+      const DgrLayer &L = net->W->layers[li];
+      maps[li] = map_of(ms, row.map, TENSORS[row.in].lvl, TENSORS[row.out].lvl);
+      kinds[li] = layer_kind(ms, f.wide3, L, maps[li], row.res != NO, ms.cm[TENSORS[row.in].lvl].n_cap,
+                             net->width(TENSORS[row.in].buf));
+      if (rule_major(kinds[li])) need = std::max(need, maps[li].km->pair_cap * L.cout);
+    }
     DGR_ALLOC(f.ybuf, A, float, need);
   }
-  const DgrMapSet &ms = f.ms;
-  const int64_t n1 = ms.cm[0].n_cap, n2 = ms.cm[1].n_cap, n4 = ms.cm[2].n_cap, n8 = ms.cm[3].n_cap;
-  auto buf = [&](int64_t rows, int cols) -> float * { return A.get<float>((size_t)rows * cols); };
   // activations (names follow model/resunet.py:598-649)
-  float *t1 = buf(n1, 32), *y1 = buf(n1, 32), *cat1 = buf(n1, 96);
-  float *t2 = buf(n2, 64), *y2 = buf(n2, 64), *cat2 = buf(n2, 128);
-  float *t4 = buf(n4, 128), *y4 = buf(n4, 128), *cat4 = buf(n4, 256);
-  float *t8 = buf(n8, 256), *y8 = buf(n8, 256), *s8 = buf(n8, 256);
-  float *u4 = buf(n4, 128), *v4 = buf(n4, 128);
-  float *u2 = buf(n2, 64), *v2 = buf(n2, 64);
-  float *u1 = buf(n1, 64), *v1 = buf(n1, 64);
-  float *h = buf(n1, 64);
+  Tensor t[N_TENSORS];
   // unit-norm output features (model/resunet.py:643-647): fused into the `final` conv's epilogue when a row's channels
   // fit one 32-channel block (every FCGF checkpoint of the reference: 16 or 32), else a pass of its own
   const bool fuse_l2 = net->normalize && net->cout <= 32;
-  float *fin = (net->normalize && !fuse_l2) ? buf(n1, net->cout) : out;
-  if (!t1 || !y1 || !cat1 || !t2 || !y2 || !cat2 || !t4 || !y4 || !cat4 || !t8 || !y8 || !s8 || !u4 ||
-      !v4 || !u2 || !v2 || !u1 || !v1 || !h || !fin)
-    return DGR_ENOMEM;
-
-  const Tensor X{const_cast<float *>(feats), net->cin, 0};
-  Tensor T1{t1, 32, 0}, Y1{y1, 32, 1}, S1{cat1 + 64, 96, 1};
-  Tensor T2{t2, 64, 0}, Y2{y2, 64, 1};
-  Tensor S2{cat2 + 64, 128, 1};
-  Tensor T4{t4, 128, 0}, Y4{y4, 128, 1}, S4{cat4 + 128, 256, 1};
-  Tensor T8{t8, 256, 0}, Y8{y8, 256, 1}, S8{s8, 256, 1};
-  Tensor U4{u4, 128, 0}, V4{v4, 128, 1};
-  Tensor U2{u2, 64, 0}, V2{v2, 64, 1};
-  Tensor U1{u1, 64, 0}, V1{v1, 64, 1};
-  Tensor S4T{cat4, 256, 1};
-  // tensors that a wide layer (conv_wide.hip) gathers are also written as split rows by their producer
-  {
-    // (middle: the tensor between the two convs of a residual block -- its only reader is the block's second conv)
-    struct { Tensor *t; int consumer, channels; int64_t rows; bool middle; } sp[] = {
-        {&T2, 4, 64, n2, false}, {&Y2, 5, 64, n2, true},
-        {&S2, 6, 64, n2, false}, {&T4, 7, 128, n4, false}, {&Y4, 8, 128, n4, true}, {&S4, 9, 128, n4, false},
-        {&T8, 10, 256, n8, false}, {&Y8, 11, 256, n8, true}, {&S8, 12, 256, n8, false}, {&U4, 13, 128, n4, false},
-        {&V4, 14, 128, n4, true}, {&U2, 16, 64, n2, false}, {&V2, 17, 64, n2, true}, {&U1, 19, 64, n1, false},
-        {&V1, 20, 64, n1, true}};
-    for (auto &e : sp) {
-      if (!net->W->layers[e.consumer].wb || (net->D == 3 && !f.wide3)) continue;
-      e.t->split.channels = e.channels;
-      e.t->split_only = e.middle;
-      DGR_ALLOC(e.t->split.planes, A, unsigned char, (size_t)e.rows * 4 * e.channels);
-      DGR_ALLOC(e.t->split.scale, A, float, e.rows);
-    }
+  for (int i = 0; i < N_TENSORS; ++i) {
+    const TensorRow &row = TENSORS[i];
+    t[i].ld = net->width(row.buf);
+    t[i].relu = row.relu;
+    if (row.buf != i) t[i].ptr = t[row.buf].ptr + row.col0;
+    else if (i == X) t[i].ptr = const_cast<float *>(feats);
+    else if (i == OUT && (!net->normalize || fuse_l2)) t[i].ptr = out;
+    else t[i].ptr = A.get<float>((size_t)ms.cm[row.lvl].n_cap * t[i].ld);
+    if (!t[i].ptr) return DGR_ENOMEM;
   }
-  Tensor S2T{cat2, 128, 1};
-  const Tensor S1T{cat1, 96, 1};
-  const Tensor H{h, 64, 1}, FIN{fin, net->cout, 0};
-  Tensor CAT4{cat4, 256, 1}, CAT2{cat2, 128, 1};
-  if (use_nbr) {
-    // row maxima of every tensor a split-operand 3-D conv reads, from ONE cleared allocation: the producers' epilogues
-    // fill them (round 3 ran a row-scale pass per consuming layer: 20 launches per forward)
-    const int64_t words = 5 * n1 + 6 * n2 + 6 * n4 + 3 * n8;
-    uint32_t *pool;
-    DGR_ALLOC(pool, A, uint32_t, words);
-    DGR_HIP_CHECK(hipMemsetAsync(pool, 0, (size_t)words * sizeof(uint32_t), stream));
-    auto take = [&](int64_t n) { uint32_t *p = pool; pool += n; return p; };
-    for (Tensor *t : {&T1, &Y1, &S1, &U1, &V1}) t->amax = take(n1);
-    for (Tensor *t : {&T2, &Y2, &S2, &CAT2, &U2, &V2}) t->amax = take(n2);
-    for (Tensor *t : {&T4, &Y4, &S4, &CAT4, &U4, &V4}) t->amax = take(n4);
-    for (Tensor *t : {&T8, &Y8, &S8}) t->amax = take(n8);
-    S2.amax2 = CAT2.amax; S2T.amax2 = CAT2.amax;   // both halves of a concatenation feed its row maxima
-    S4.amax2 = CAT4.amax; S4T.amax2 = CAT4.amax;
-    if (f.wide3) {
-      // tensors written by a reduction have no row maxima: the two that an output-stationary kernel reads (S8: conv4_tr,
-      // CAT4: conv3_tr) get them from a pass in front of that launch, the others have none (their readers gather split rows)
-      for (Tensor *t : {&Y4, &S4, &T8, &Y8, &V4}) t->amax = nullptr;
-      S4.amax2 = S4T.amax2 = nullptr;
-      S8.amax_pending = CAT4.amax_pending = true;
-      // ... and the two wide-layer inputs that come out of an output-stationary kernel (conv3, conv4_tr) are split in
-      // front of their consumer
-      T4.split_pending = U4.split_pending = true;
-    }
+  DGR_CHECK(derive_forms(f, kinds, t));
+
+  for (int li = 0; li < N_LAYERS; ++li) {
+    const LayerRow &row = LAYERS[li];
+    DGR_CHECK(f.conv(li, kinds[li], t[row.in], maps[li], TENSORS[row.in].lvl, TENSORS[row.out].lvl, t[row.out],
+                     row.res != NO ? &t[row.res] : nullptr, fuse_l2 && row.out == OUT));
+  }
+  if (t[OUT].ptr != out) {
+    DGR_CHECK(dgr_l2_normalize_rows(t[OUT].ptr, net->cout, out, net->cout, net->cout, 0, ms.cm[0].n_dev, ms.cm[0].n_cap, stream));
+    t[OUT].ptr = out;
   }
 
-  if (use_nbr && !getenv("DGR_NO_DSPLIT")) {
-    // the middle tensor of a residual block at the two finest levels goes from dense-tile kernel to dense-tile kernel:
-    // written as that kernel's operand pieces, and as nothing else (the conditions are those of `o.dense` in Fwd::conv)
-    static const bool os_lists = getenv("DGR_OS_LISTS") != nullptr;
-    auto dense_layer = [&](int l, int64_t rows) {
-      const DgrLayer &L = net->W->layers[l];
-      return L.w16b && L.w16d && !dgr_exact_f32() && !os_lists && dgr_conv_dense_supported(L.cin, L.cin_pad, L.cout) &&
-             dgr_fits_32bit_offsets(rows, L.cin);
-    };
-    struct { Tensor *t; int producer; int64_t rows; } mid[] = {{&Y1, 1, n1}, {&Y2, 4, n2}, {&V2, 16, n2}, {&V1, 19, n1}};
-    for (auto &e : mid)
-      if (dense_layer(e.producer, e.rows) && dense_layer(e.producer + 1, e.rows) && e.t->ld == net->W->layers[e.producer].cout) {
-        e.t->dsplit = reinterpret_cast<unsigned char *>(e.t->ptr);
-        e.t->dsplit_only = true;
-      }
-  }
-
-  int li = 0;
-  // encoder
-  if (conv1_fused) {                                                   // conv1 + norm1
-    const DgrLayer &L0 = net->W->layers[0];
-    int32_t *pc;
-    DGR_ALLOC(pc, A, int32_t, 1);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (f.prof) {
-      e0 = ctx->events.next(); e1 = ctx->events.next();
-      DGR_HIP_CHECK(hipEventRecord(e0, stream));
-    }
-    const char *k1name = "conv1_grid_kernel";
-    DGR_CHECK(dgr_conv1_probe(A, ms.cm[0], net->conv1_ks, feats, net->cin, net->cin, L0.w, L0.shift, t1, 32, pc, stream,
-                              L0.wc, &k1name, T1.amax));
-    if (f.prof) {
-      DGR_HIP_CHECK(hipEventRecord(e1, stream));
-      ctx->conv_spans.push_back({e0, e1});
-      ctx->gemm_spans.push_back({e0, e1});
-      ctx->conv_kinds.push_back(k1name);
-    }
-    LayerRun &r0 = net->runs[0];
-    r0 = LayerRun();
-    r0.n_in = r0.n_out = ms.cm[0].n_dev;
-    r0.K = L0.K;
-    r0.fused_pairs = pc;
-    li++;
-  } else {
-    DGR_CHECK(f.conv(li++, X, &ms.conv1, false, 0, 0, T1, nullptr));
-  }
-  DGR_CHECK(f.conv(li++, T1, &ms.same[0], false, 0, 0, Y1, nullptr));  // block1
-  DGR_CHECK(f.conv(li++, Y1, &ms.same[0], false, 0, 0, S1, &T1));
-  DGR_CHECK(f.conv(li++, S1, &ms.down[0], false, 0, 1, T2, nullptr));  // conv2 (stride 2) + norm2
-  DGR_CHECK(f.conv(li++, T2, &ms.same[1], false, 1, 1, Y2, nullptr));  // block2
-  DGR_CHECK(f.conv(li++, Y2, &ms.same[1], false, 1, 1, S2, &T2));
-  DGR_CHECK(f.conv(li++, S2, &ms.down[1], false, 1, 2, T4, nullptr));  // conv3
-  DGR_CHECK(f.conv(li++, T4, &ms.same[2], false, 2, 2, Y4, nullptr));  // block3
-  DGR_CHECK(f.conv(li++, Y4, &ms.same[2], false, 2, 2, S4, &T4));
-  DGR_CHECK(f.conv(li++, S4, &ms.down[2], false, 2, 3, T8, nullptr));  // conv4
-  DGR_CHECK(f.conv(li++, T8, &ms.same[3], false, 3, 3, Y8, nullptr));  // block4
-  DGR_CHECK(f.conv(li++, Y8, &ms.same[3], false, 3, 3, S8, &T8));
-  // decoder: transposed convs reuse the strided maps with in/out swapped
-  DGR_CHECK(f.conv(li++, S8, &ms.down[2], true, 3, 2, U4, nullptr));   // conv4_tr + norm4_tr
-  DGR_CHECK(f.conv(li++, U4, &ms.same[2], false, 2, 2, V4, nullptr));  // block4_tr
-  DGR_CHECK(f.conv(li++, V4, &ms.same[2], false, 2, 2, S4T, &U4));     // -> cat4[:, :128]
-  DGR_CHECK(f.conv(li++, CAT4, &ms.down[1], true, 2, 1, U2, nullptr));  // conv3_tr
-  DGR_CHECK(f.conv(li++, U2, &ms.same[1], false, 1, 1, V2, nullptr));   // block3_tr
-  DGR_CHECK(f.conv(li++, V2, &ms.same[1], false, 1, 1, S2T, &U2));
-  DGR_CHECK(f.conv(li++, CAT2, &ms.down[0], true, 1, 0, U1, nullptr));  // conv2_tr
-  DGR_CHECK(f.conv(li++, U1, &ms.same[0], false, 0, 0, V1, nullptr));   // block2_tr
-  DGR_CHECK(f.conv(li++, V1, &ms.same[0], false, 0, 0, S1T, &U1));
-  const Tensor CAT1{cat1, 96, 1};
-  DGR_CHECK(f.conv(li++, CAT1, nullptr, false, 0, 0, H, nullptr));      // conv1_tr (k=1), ReLU pending
-  f.l2_next = fuse_l2;
-  DGR_CHECK(f.conv(li++, H, nullptr, false, 0, 0, FIN, nullptr));       // final (k=1) + bias (+ normalisation)
-  if (net->normalize && !fuse_l2)
-    DGR_CHECK(dgr_l2_normalize_rows(fin, net->cout, out, net->cout, net->cout, 0, ms.cm[0].n_dev, n1, stream));
-
-  auto &I = net->inter;
   net->run_generation = ctx->arena.generation;
-  I.clear();
-  I["s1"] = {S1.ptr, 96, 32, ms.cm[0].n_dev};
-  I["s2"] = {S2.ptr, 128, 64, ms.cm[1].n_dev, ms.cm[1].canon};
-  I["s4"] = {S4.ptr, 256, 128, ms.cm[2].n_dev, ms.cm[2].canon};
-  I["s8"] = {S8.ptr, 256, 256, ms.cm[3].n_dev, ms.cm[3].canon};
-  I["s4_tr"] = {cat4, 256, 128, ms.cm[2].n_dev, ms.cm[2].canon};
-  I["s2_tr"] = {cat2, 128, 64, ms.cm[1].n_dev, ms.cm[1].canon};
-  I["s1_tr"] = {cat1, 96, 64, ms.cm[0].n_dev};
-  // every named tensor, in the representations this forward really wrote (dgr_net_get_tensor)
-  // (the same names every forward: the entries are overwritten in place)
-  auto reg =[&](const char *name, const Tensor &t, int cols, int lvl) {
-    DgrTensorRec r;
-    r.f32 = (t.split_only || t.dsplit_only) ? nullptr : t.ptr;
-    r.ld = t.ld; r.cols = cols;
-    r.amax = t.amax;
-    r.planes = t.split.planes; r.scale = t.split.scale;
-    r.dsplit = t.dsplit;
-    r.n_dev = ms.cm[lvl].n_dev; r.canon = ms.cm[lvl].canon;
-    net->tensors[name] = r;
-  };
-  reg("T1", T1, 32, 0); reg("Y1", Y1, 32, 0); reg("S1", S1, 32, 0);
-  reg("T2", T2, 64, 1); reg("Y2", Y2, 64, 1); reg("S2", S2, 64, 1);
-  reg("T4", T4, 128, 2); reg("Y4", Y4, 128, 2); reg("S4", S4, 128, 2);
-  reg("T8", T8, 256, 3); reg("Y8", Y8, 256, 3); reg("S8", S8, 256, 3);
-  reg("U4", U4, 128, 2); reg("V4", V4, 128, 2); reg("S4T", S4T, 128, 2); reg("CAT4", CAT4, 256, 2);
-  reg("U2", U2, 64, 1); reg("V2", V2, 64, 1); reg("S2T", S2T, 64, 1); reg("CAT2", CAT2, 128, 1);
-  reg("U1", U1, 64, 0); reg("V1", V1, 64, 0); reg("S1T", S1T, 64, 0); reg("CAT1", CAT1, 96, 0);
-  reg("H", H, 64, 0);
-  reg("OUT", Tensor{out, net->cout, 0}, net->cout, 0);
-
+  std::copy(t, t + N_TENSORS, net->tensors);
+  std::copy(ms.cm, ms.cm + 4, net->levels);
   return DGR_OK;
 }
 
@@ -1051,90 +1048,96 @@ extern "C" int dgr_debug_conv_layer(dgr_ctx *ctx, dgr_net *net, int layer, const
   const int64_t n_cap = f.ms.cm[0].n_cap;
   if (!f.ms.use_nbr) DGR_ALLOC(f.ybuf, A, float, f.ms.same[0].pair_cap * L.cout);
   Tensor tin{const_cast<float *>(in), L.cin, in_relu}, tout{out, L.cout, 0};
-  if (L.wb && !f.ms.use_nbr) {
+  const MapRef m = map_of(f.ms, M_SAME, 0, 0);
+  const Kind kind = layer_kind(f.ms, false, L, m, false, n_cap, tin.ld);
+  // a tensor that did not come out of one of the conv kernels: the forms the layer reads are pending
+  if (kind == K_WIDE) {
     tin.split.channels = L.cin;
     DGR_ALLOC(tin.split.planes, A, unsigned char, (size_t)n_cap * 4 * L.cin);
     DGR_ALLOC(tin.split.scale, A, float, n_cap);
-    DGR_CHECK(dgr_split_rows(in, L.cin, in_relu, f.ms.cm[0].n_dev, n_cap, tin.split, stream));
+    tin.split_pending = true;
   }
-  DGR_CHECK(f.conv(layer, tin, &f.ms.same[0], false, 0, 0, tout, nullptr));
+  if (reads_amax(kind)) {
+    DGR_ALLOC(tin.amax, A, uint32_t, n_cap);
+    tin.amax_pending = true;
+  }
+  DGR_CHECK(f.conv(layer, kind, tin, m, 0, 0, tout, nullptr, false));
   DGR_CHECK(dgr_ctx_check_flag(ctx, stream));   // synchronises the stream
   dgr_net_invalidate_runs(net);
   return DGR_OK;
 }
 
-extern "C" int dgr_net_get_intermediate(dgr_ctx *ctx, dgr_net *net, const char *name, float *host_out,
-                                        int64_t capacity, int64_t *rows, int64_t *cols) {
-  DGR_REQUIRE(ctx && net && name && rows && cols, "NULL argument");
-  auto it = net->inter.find(name);
-  DGR_REQUIRE(it != net->inter.end() && it->second.n_dev, "no intermediate named '%s' (run a forward first)", name);
+// ---- read-back of the last forward's tensors: two entries that differ in what they call the tensors
+// tensor `i` (NO: the name was not found) is there to be read
+static int readable(dgr_ctx *ctx, const dgr_net *net, int i, const char *noun, const char *name) {
+  DGR_REQUIRE(i > X && net->levels[TENSORS[i].lvl].n_dev, "no %s named '%s' (run a forward first)", noun, name);
   DGR_REQUIRE(net->run_generation == ctx->arena.generation,
               "the activations of the last forward are gone: a later call on this context reused its workspace");
-  const DgrTensorRef &t = it->second;
-  int32_t n = 0;
-  DGR_HIP_CHECK(hipDeviceSynchronize());
-  DGR_HIP_CHECK(hipMemcpy(&n, t.n_dev, sizeof(int32_t), hipMemcpyDeviceToHost));
-  *rows = n;
-  *cols = t.cols;
-  if (host_out) {
-    DGR_REQUIRE(capacity >= (int64_t)n * t.cols, "host buffer too small");
-    if (!t.canon) {
-      DGR_HIP_CHECK(hipMemcpy2D(host_out, (size_t)t.cols * sizeof(float), t.ptr, (size_t)t.ld * sizeof(float),
-                                (size_t)t.cols * sizeof(float), (size_t)n, hipMemcpyDeviceToHost));
-    } else {   // rows back in first-occurrence order (coarse 6-D maps are numbered in bucket order)
-      std::vector<float> tmp((size_t)n * t.cols);
-      std::vector<int32_t> canon(n);
-      DGR_HIP_CHECK(hipMemcpy2D(tmp.data(), (size_t)t.cols * sizeof(float), t.ptr, (size_t)t.ld * sizeof(float),
-                                (size_t)t.cols * sizeof(float), (size_t)n, hipMemcpyDeviceToHost));
-      DGR_HIP_CHECK(hipMemcpy(canon.data(), t.canon, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-      for (int32_t p = 0; p < n; ++p)
-        memcpy(host_out + (size_t)canon[p] * t.cols, tmp.data() + (size_t)p * t.cols, (size_t)t.cols * sizeof(float));
-    }
-    for (int64_t i = 0; i < (int64_t)n * t.cols; ++i) host_out[i] = host_out[i] > 0.f ? host_out[i] : 0.f;
-  }
   return DGR_OK;
 }
 
-extern "C" int dgr_net_get_tensor(dgr_ctx *ctx, dgr_net *net, const char *name, int repr, void *host_out,
-                                  int64_t capacity_bytes, int64_t *rows, int64_t *row_bytes) {
-  DGR_REQUIRE(ctx && net && name && rows && row_bytes, "NULL argument");
-  auto it = net->tensors.find(name);
-  DGR_REQUIRE(it != net->tensors.end() && it->second.n_dev, "no tensor named '%s' (run a forward first)", name);
-  DGR_REQUIRE(net->run_generation == ctx->arena.generation,
-              "the activations of the last forward are gone: a later call on this context reused its workspace");
-  const DgrTensorRec &t = it->second;
-  const void *src = nullptr;
-  size_t rb = 0, ld = 0;   // bytes per row: returned / in memory
-  const char *what = "";
-  switch (repr) {
-    case DGR_TENSOR_F32: src = t.f32; rb = (size_t)t.cols * 4; ld = (size_t)t.ld * 4; what = "f32 rows"; break;
-    case DGR_TENSOR_AMAX: src = t.amax; rb = ld = 4; what = "row maxima"; break;
-    case DGR_TENSOR_SPLIT_PLANES: src = t.planes; rb = ld = (size_t)t.cols * 4; what = "split rows"; break;
-    case DGR_TENSOR_SPLIT_SCALE: src = t.scale; rb = ld = 4; what = "split-row scales"; break;
-    case DGR_TENSOR_DENSE_SPLIT: src = t.dsplit; rb = ld = (size_t)t.cols * 4; what = "dense split rows"; break;
-    default: DGR_REQUIRE(false, "dgr_net_get_tensor: unknown representation %d", repr);
-  }
-  DGR_REQUIRE(src != nullptr, "the last forward did not write tensor '%s' as %s", name, what);
+// ... and one of its forms -- rows of rb bytes, `ld` bytes apart on the device -- comes back in the caller's row order
+static int read_rows(const DgrCoordMap &cm, const void *src, size_t rb, size_t ld, void *host_out, int64_t capacity_bytes,
+                     int64_t *rows) {
   int32_t n = 0;
   DGR_HIP_CHECK(hipDeviceSynchronize());
-  DGR_HIP_CHECK(hipMemcpy(&n, t.n_dev, sizeof(int32_t), hipMemcpyDeviceToHost));
+  DGR_HIP_CHECK(hipMemcpy(&n, cm.n_dev, sizeof(int32_t), hipMemcpyDeviceToHost));
   *rows = n;
-  *row_bytes = (int64_t)rb;
   if (!host_out) return DGR_OK;
   DGR_REQUIRE(capacity_bytes >= (int64_t)n * (int64_t)rb, "host buffer too small");
-  if (!t.canon) {
+  if (!cm.canon) {
     DGR_HIP_CHECK(hipMemcpy2D(host_out, rb, src, ld, rb, (size_t)n, hipMemcpyDeviceToHost));
   } else {   // rows back in first-occurrence order (coarse 6-D maps are numbered in bucket order)
     std::vector<unsigned char> tmp((size_t)n * rb);
     std::vector<int32_t> canon(n);
     DGR_HIP_CHECK(hipMemcpy2D(tmp.data(), rb, src, ld, rb, (size_t)n, hipMemcpyDeviceToHost));
-    DGR_HIP_CHECK(hipMemcpy(canon.data(), t.canon, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    DGR_HIP_CHECK(hipMemcpy(canon.data(), cm.canon, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int32_t p = 0; p < n; ++p) {
       DGR_REQUIRE(canon[p] >= 0 && canon[p] < n, "dgr_net_get_tensor: row numbering out of range");
       memcpy(static_cast<unsigned char *>(host_out) + (size_t)canon[p] * rb, tmp.data() + (size_t)p * rb, rb);
     }
   }
   return DGR_OK;
+}
+
+extern "C" int dgr_net_get_intermediate(dgr_ctx *ctx, dgr_net *net, const char *name, float *host_out,
+                                        int64_t capacity, int64_t *rows, int64_t *cols) {
+  DGR_REQUIRE(ctx && net && name && rows && cols, "NULL argument");
+  int i = NO;
+  for (const auto &e : INTERMEDIATES)
+    if (!strcmp(name, e.name)) i = e.t;
+  DGR_CHECK(readable(ctx, net, i, "intermediate", name));
+  const Tensor &t = net->tensors[i];
+  *cols = net->width((Tn)i);
+  DGR_CHECK(read_rows(net->levels[TENSORS[i].lvl], t.ptr, (size_t)*cols * 4, (size_t)t.ld * 4, host_out, capacity * 4, rows));
+  if (host_out)
+    for (int64_t j = 0; j < *rows * *cols; ++j) host_out[j] = host_out[j] > 0.f ? host_out[j] : 0.f;
+  return DGR_OK;
+}
+
+extern "C" int dgr_net_get_tensor(dgr_ctx *ctx, dgr_net *net, const char *name, int repr, void *host_out,
+                                  int64_t capacity_bytes, int64_t *rows, int64_t *row_bytes) {
+  DGR_REQUIRE(ctx && net && name && rows && row_bytes, "NULL argument");
+  int i = NO;
+  for (int j = 0; j < N_TENSORS; ++j)
+    if (!strcmp(name, TENSORS[j].name)) i = j;
+  DGR_CHECK(readable(ctx, net, i, "tensor", name));
+  const Tensor &t = net->tensors[i];
+  const size_t cols = (size_t)net->width((Tn)i);
+  const void *src = nullptr;
+  size_t rb = 0, ld = 0;   // bytes per row: returned / in memory
+  const char *what = "";
+  switch (repr) {
+    case DGR_TENSOR_F32: src = (t.split_only || t.dsplit_only) ? nullptr : t.ptr; rb = cols * 4; ld = (size_t)t.ld * 4; what = "f32 rows"; break;
+    case DGR_TENSOR_AMAX: src = t.amax; rb = ld = 4; what = "row maxima"; break;
+    case DGR_TENSOR_SPLIT_PLANES: src = t.split.planes; rb = ld = cols * 4; what = "split rows"; break;
+    case DGR_TENSOR_SPLIT_SCALE: src = t.split.scale; rb = ld = 4; what = "split-row scales"; break;
+    case DGR_TENSOR_DENSE_SPLIT: src = t.dsplit; rb = ld = cols * 4; what = "dense split rows"; break;
+    default: DGR_REQUIRE(false, "dgr_net_get_tensor: unknown representation %d", repr);
+  }
+  DGR_REQUIRE(src != nullptr, "the last forward did not write tensor '%s' as %s", name, what);
+  *row_bytes = (int64_t)rb;
+  return read_rows(net->levels[TENSORS[i].lvl], src, rb, ld, host_out, capacity_bytes, rows);
 }
 
 extern "C" int dgr_net_layer_stats(dgr_ctx *ctx, dgr_net *net, int layer, int64_t stats[8]) {
@@ -1150,13 +1153,13 @@ extern "C" int dgr_net_layer_stats(dgr_ctx *ctx, dgr_net *net, int layer, int64_
   DGR_HIP_CHECK(hipMemcpy(&n_in, r.n_in, sizeof(int32_t), hipMemcpyDeviceToHost));
   DGR_HIP_CHECK(hipMemcpy(&n_out, r.n_out, sizeof(int32_t), hipMemcpyDeviceToHost));
   int64_t P = n_out, kne = 1;
-  if (r.os) {
+  if (on_tables(r.kind)) {
     int64_t counts[27];
     DGR_CHECK(dgr_nbr_counts(r.nbr, r.n_out, counts));
     P = 0;
     kne = 0;
     for (int k = 0; k < 27; ++k) { P += counts[k]; kne += counts[k] > 0; }
-  } else if (r.fused_pairs) {
+  } else if (r.kind == K_CONV1_FUSED) {
     int32_t pc = 0;
     DGR_HIP_CHECK(hipMemcpy(&pc, r.fused_pairs, sizeof(int32_t), hipMemcpyDeviceToHost));
     P = pc;
@@ -1183,8 +1186,7 @@ extern "C" int dgr_net_rerun_layer(dgr_ctx *ctx, dgr_net *net, int layer, int re
   DGR_REQUIRE(r.n_in && r.n_out, "run a forward first");
   DGR_REQUIRE(net->run_generation == ctx->arena.generation,
               "the kernel maps of the last forward are gone: a later call on this context reused its workspace");
-  DGR_REQUIRE(!r.fused_pairs, "layer %d ran fused with its neighbour search; not re-runnable", layer);
-  const DgrLayer &L = net->W->layers[layer];
+  DGR_REQUIRE(r.kind != K_CONV1_FUSED, "layer %d ran fused with its neighbour search; not re-runnable", layer);
   // on the context's CU-masked stream if it has one (ctx->num_cus is then the share's size), else on the null stream
   hipStream_t st = ctx->part_stream;
   hipEvent_t e0, e1, e2;
@@ -1192,20 +1194,7 @@ extern "C" int dgr_net_rerun_layer(dgr_ctx *ctx, dgr_net *net, int layer, int re
   float tg = 0.f, tr = 0.f;
   for (int i = 0; i < reps + 1; ++i) {  // first iteration = warm-up
     DGR_HIP_CHECK(hipEventRecord(e0, st));
-    if (r.os)
-      DGR_CHECK(dgr_conv_os_launch(r.os_launch, st));
-    else if (r.small_cin)
-      DGR_CHECK(dgr_conv_small_cin(r.launch.in, r.launch.in_ld, r.launch.in_relu, L.cin, L.w, L.wq, L.shift, r.km, r.n_out,
-                                   r.n_out_cap, r.launch.out, r.launch.out_ld, st));
-    else if (L.wb && r.has_reduce)
-      DGR_CHECK(dgr_conv_wide_launch(r.launch, r.split_in, L.wb, L.wb_piece, L.w_unscale, ctx->num_cus, st));
-    else
-      DGR_CHECK(dgr_conv_launch(r.launch, ctx->num_cus, st));
-    DGR_HIP_CHECK(hipEventRecord(e1, st));
-    if (r.has_reduce && !r.small_cin && !r.os)
-      DGR_CHECK(dgr_reduce_rows(r.launch.y, L.cout, r.red_ptr, r.red_pos, r.n_out, r.n_out_cap,
-                                r.split_only ? nullptr : r.launch.out, r.launch.out_ld, L.shift, r.res, r.res_ld, r.res_relu, st,
-                                r.split_out.planes ? &r.split_out : nullptr, r.out_relu));
+    DGR_CHECK(run_layer(ctx, net, layer, st, e1));
     DGR_HIP_CHECK(hipEventRecord(e2, st));
     DGR_HIP_CHECK(hipEventSynchronize(e2));
     float a = 0.f, b = 0.f;

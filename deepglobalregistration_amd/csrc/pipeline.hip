@@ -6,19 +6,6 @@
 
 #include "dgr_internal.h"
 
-int dgr_registration_launch_ctx(dgr_ctx *ctx, const float *xyz0, const float *xyz1, const int64_t *idx1,
-                                const float *lw, int is_logit, float clip, const int64_t *off0_dev,
-                                const int64_t *off0_host, int npairs, int64_t total_rows, float q, int max_iter, int max_break,
-                                double ratio, int skip_refine, int gate, float eps, float *weights_out,
-                                DgrRegResult *results_dev, hipStream_t stream);
-int dgr_ctx_new_flag(dgr_ctx *ctx, hipStream_t stream);
-int dgr_ctx_check_flag(dgr_ctx *ctx, hipStream_t stream);
-int dgr_net_out_channels(const dgr_net *net);
-void dgr_net_invalidate_runs(dgr_net *net);
-int dgr_net_in_channels(const dgr_net *net);
-int dgr_net_dim(const dgr_net *net);
-const dgr_ctx *dgr_net_ctx(const dgr_net *net);
-
 // ---- 6-D coordinates (:261-262) and inlier features (:185-208) ----------------------------------
 __global__ void inlier_inputs_kernel(const int32_t *__restrict__ coords0, const float *__restrict__ xyz0,
                                      int64_t N0, const int32_t *__restrict__ coords1,

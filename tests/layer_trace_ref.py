@@ -4,8 +4,8 @@ each other (CPU only; used by tests/test_layer_trace_cpu.py and tests/test_gpu_l
   * split2 / row_scale_of / row_amax_bits: csrc/split.h restated with np.float16 round-to-nearest;
   * encode / decode of the 6-D split rows (dgr_split_row_offset) and of the 3-D dense split rows (DESIGN.md section 3,
     conv_dense.hip), decoders returning (h + m) / scale in float64;
-  * LAYERS: the 23 convs in forward order with their input, kernel map, residual and ReLU flags (the Fwd::conv call
-    list of net.hip);
+  * LAYERS: the 23 convs in forward order with their input, kernel map, residual and ReLU flags (the LAYERS table
+    of net.hip);
   * unit_truth: float64 output of one layer and the per-element magnitude bound B = |shift| + sum |x||W| + |res|;
   * unit_norm: v / (|v| + 1e-8) with B propagated to first order;
   * unit_f32: the same layer in the reference's own float32 arithmetic (oracle.resunet.sparse_conv + batch_norm), the
@@ -129,7 +129,7 @@ def resplit_mismatches(h, m):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the 23 layers as the forward runs them (net.hip, the Fwd::conv call list)
+# the 23 layers as the forward runs them (net.hip, the LAYERS and TENSORS tables)
 # ---------------------------------------------------------------------------------------------------------------------
 # pending ReLU of every tensor (consumers apply max(x, 0) when reading)
 RELU = {'X': 0, 'H': 1, 'OUT': 0, 'CAT4': 1, 'CAT2': 1, 'CAT1': 1}

@@ -1,4 +1,4 @@
-"""Both sides of the 2-GB guard of the dense-tile kernel (net.hip, `Fwd::conv`): `sparse_conv_dense_f16x2` addresses its
+"""Both sides of the 2-GB guard of the dense-tile kernel (net.hip, `layer_kind`): `sparse_conv_dense_f16x2` addresses its
 input through buffer loads with 32-bit byte offsets, so a same-stride C <= 64 layer whose INPUT tensor reaches 2 GB stays
 on the list-based kernel (`sparse_conv_os`, 32-bit ELEMENT offsets: 16 GB).  One FCGF forward over 8.7 M voxels puts the
 guard on both sides at once: the level-0 64-channel tensors (256 B per row) are 2.2 GB, the level-0 32-channel ones

@@ -108,7 +108,7 @@ OS_FAMILY = ('sparse_conv_os<', 'sparse_conv_dense_f16x2', 'sparse_conv_up_f16x2
 
 
 def expected_family(D, cin, mode, li, L, ci, co):
-    """Kernel family of layer li (ci -> co channels) by net shape and mode: the dispatch of Fwd::conv as a table."""
+    """Kernel family of layer li (ci -> co channels) by net shape and mode: the dispatch of layer_kind (net.hip) as a table."""
     if L['map'] is None:
         return 'identity_conv_kernel'
     fused3 = D == 3 and cin <= 8
