@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib, ops
+from .. import _args, _lib, ops
 from ..model import load_model
 from ..sparse import SparseTensor
 from ..util.timer import Timer
@@ -339,6 +339,24 @@ class DeepGlobalRegistration:
         self.feat_timer.toc()
         return FragmentBank.from_tensors(bank_coords, torch.cat(xyz), torch.cat(feats), np.asarray(off, np.int64))
 
+    def _check_bank_device(self, bank):
+        bd = torch.device(bank.device)    # ('cuda' without an index is the current device: not told apart here)
+        if bd.type != self.device.type or (None not in (bd.index, self.device.index) and bd.index != self.device.index):
+            raise ValueError(f'the bank is on {bank.device}, this object on {self.device}')
+
+    def _scored_pairs_args(self, bank, pairs, T, radius):
+        """What `score_pairs` and `optimize_scene` open with: the bank's device, the pair ids and the poses checked as in
+        `register_pairs` / `ops.check_score_args`.  Returns (ids int32 [n,2], T float64 [n,4,4] with the last row set to
+        (0, 0, 0, 1), radius: 2 voxels when None)."""
+        from .fragment_bank import pair_groups
+        self._check_bank_device(bank)
+        ids = np.concatenate([g for _, g in pair_groups(bank, pairs, 1)])
+        radius = 2 * self.voxel_size if radius is None else radius
+        _, _, T, radius = ops.check_score_args(len(bank.xyz), bank.off, ids, T, radius)
+        T = T.reshape(len(ids), 4, 4).copy()
+        T[:, 3] = (0, 0, 0, 1)                    # (the library ignores the last row; an inverse must not see it)
+        return ids, T, radius
+
     def register_pairs(self, bank, pairs, batch_pairs=6, safeguard=False, icp=False, skip_refinement=False,
                        forced_logits=None, override_idx1=None):
         """Registers `pairs` ([n,2] integers: fragment i of `bank` onto fragment j) through the fused path
@@ -348,9 +366,7 @@ class DeepGlobalRegistration:
         The two harness hooks are lists with one entry per PAIR: forced_logits[k] one value per row of pair k's
         fragment 0, override_idx1[k] rows of pair k's fragment 1 (-1 = keep the match)."""
         from .fragment_bank import group_hooks, pair_groups
-        bd = torch.device(bank.device)    # ('cuda' without an index is the current device: not told apart here)
-        if bd.type != self.device.type or (None not in (bd.index, self.device.index) and bd.index != self.device.index):
-            raise ValueError(f'the bank is on {bank.device}, this object on {self.device}')
+        self._check_bank_device(bank)
         if bank.n_out != self.fcgf_model.out_channels:
             raise ValueError(f'the bank holds {bank.n_out}-wide features, the FCGF model writes '
                              f'{self.fcgf_model.out_channels}')
@@ -380,17 +396,9 @@ class DeepGlobalRegistration:
         share of j's rows) and `overlap` = max(fitness, fitness_reverse) -- the reference's `compute_overlap_ratio`
         (util/pointcloud.py:72-80) at that radius.  Only the bank's `xyz` is read: neither network runs and the feature
         width does not matter.  The bank's device and the pair ids are checked as in `register_pairs`."""
-        from .fragment_bank import pair_groups
         from .pair_score import scores_from_sums
-        bd = torch.device(bank.device)
-        if bd.type != self.device.type or (None not in (bd.index, self.device.index) and bd.index != self.device.index):
-            raise ValueError(f'the bank is on {bank.device}, this object on {self.device}')
-        ids = np.concatenate([g for _, g in pair_groups(bank, pairs, 1)])
+        ids, T, radius = self._scored_pairs_args(bank, pairs, T, radius)
         n = len(ids)
-        radius = 2 * self.voxel_size if radius is None else radius
-        _, _, T, radius = ops.check_score_args(len(bank.xyz), bank.off, ids, T, radius)
-        T = T.reshape(n, 4, 4).copy()
-        T[:, 3] = (0, 0, 0, 1)                    # (the library ignores the last row; the inverse must not see it)
         try:
             T_inv = np.linalg.inv(T)
         except np.linalg.LinAlgError as e:
@@ -426,16 +434,9 @@ class DeepGlobalRegistration:
         bool, `reachable` [n] bool, `objective_initial` / `objective_final` (F* at the start of pass 1 / the end of
         pass 2), `iterations` and `converged` (both passes), `mu`."""
         from . import pose_graph as pgm
-        from .fragment_bank import pair_groups
-        bd = torch.device(bank.device)
-        if bd.type != self.device.type or (None not in (bd.index, self.device.index) and bd.index != self.device.index):
-            raise ValueError(f'the bank is on {bank.device}, this object on {self.device}')
-        ids = np.concatenate([g for _, g in pair_groups(bank, pairs, 1)]).astype(np.int64)
+        ids, T, radius = self._scored_pairs_args(bank, pairs, T, radius)
+        ids = ids.astype(np.int64)
         m, n = len(ids), len(bank)
-        radius = 2 * self.voxel_size if radius is None else radius
-        _, _, T, radius = ops.check_score_args(len(bank.xyz), bank.off, ids, T, radius)
-        T = T.reshape(m, 4, 4).copy()
-        T[:, 3] = (0, 0, 0, 1)
         if not 0 <= reference_node < n:
             raise ValueError(f'reference node {reference_node} outside [0, {n})')
         if not (edge_prune_threshold >= 0 and edge_prune_threshold <= 1):
@@ -501,15 +502,12 @@ class DeepGlobalRegistration:
         order of their first point: `xyz` float64 [V,3], `count` int32 [V], `first_fragment` int64 [V] (the fragment that
         voxel's first point belongs to), and `dropped` (int): points that are not finite or leave the int32 lattice.
         Neither network runs.  The bank's device and the fragment ids are checked as in `score_pairs`."""
-        bd = torch.device(bank.device)
-        if bd.type != self.device.type or (None not in (bd.index, self.device.index) and bd.index != self.device.index):
-            raise ValueError(f'the bank is on {bank.device}, this object on {self.device}')
+        self._check_bank_device(bank)
         n = len(bank)
-        poses = poses.detach().cpu().numpy() if torch.is_tensor(poses) else np.asarray(poses)
+        poses = _args.host(poses)
         if poses.shape != (n, 4, 4):
             raise ValueError(f'poses must be [{n},4,4], got {poses.shape}')
-        if isinstance(min_points, (bool, np.bool_)) or not isinstance(min_points, (int, np.integer)) or min_points < 1:
-            raise ValueError(f'min_points must be an integer >= 1, got {min_points!r}')
+        min_points = _args.integer(min_points, 'min_points', lambda v: v >= 1, 'an integer >= 1')
         voxel_size = self.voxel_size if voxel_size is None else voxel_size
         if clouds is None:
             parts, off, rows = None, bank.off, len(bank.xyz)
@@ -558,7 +556,7 @@ class DeepGlobalRegistration:
         c0, x0, off0, c1, x1, off1 = self._collated(input_dict)
         n = len(off0) - 1
         T_gt = input_dict['T_gt']
-        T_gt = (T_gt.detach().cpu().numpy() if torch.is_tensor(T_gt) else np.asarray(T_gt)).astype(np.float64)
+        T_gt = _args.host(T_gt).astype(np.float64)
         if T_gt.shape != (n, 4, 4):
             raise ValueError(f'T_gt must be [{n},4,4], got {T_gt.shape}')
         radius = 2 * self.voxel_size if matching_radius is None else matching_radius

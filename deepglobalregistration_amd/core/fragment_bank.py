@@ -8,6 +8,8 @@ off[i]:off[i+1]; `off` is a host int64 array.  The library holds no bank object:
 import numpy as np
 import torch
 
+from .. import _args
+
 FEATURE_WIDTHS = (16, 32, 64)   # the widths the feature matcher is built for (csrc/knn_common.h)
 
 
@@ -33,6 +35,7 @@ class FragmentBank:
             raise ValueError('coords, xyz and F must have the same number of rows')
         if not (coords.device == xyz.device == F.device):
             raise ValueError('coords, xyz and F must be on one device')
+        # (not _args.fragment_offsets: a bank's offsets start at 0 exactly, and the two faults have messages of their own)
         off = np.asarray(off.cpu() if torch.is_tensor(off) else off)
         if off.ndim != 1 or len(off) < 2 or not np.issubdtype(off.dtype, np.integer):
             raise ValueError('off must be a 1-D integer array [nfrag+1]')
@@ -76,16 +79,9 @@ class FragmentBank:
 def pair_groups(bank, pairs, batch_pairs):
     """`pairs` ([n,2] integers) checked against the bank and cut into consecutive groups of `batch_pairs` in the given
     order: a list of (first pair index, ids int32 [g,2]).  ValueError for an empty list or an id outside the bank."""
-    ids = np.asarray(pairs)
-    if ids.size == 0:
-        raise ValueError('the pair list is empty')
-    if ids.ndim != 2 or ids.shape[1] != 2 or not np.issubdtype(ids.dtype, np.integer):
-        raise ValueError('pairs must be an [n,2] integer array')
-    if (ids < 0).any() or (ids >= len(bank)).any():
-        raise ValueError(f'pair id outside [0, {len(bank)})')
+    ids = _args.pair_ids(np.asarray(pairs), len(bank), 'pairs')   # (np.asarray: a device tensor is not taken here)
     if int(batch_pairs) < 1:
         raise ValueError('batch_pairs must be at least 1')
-    ids = ids.astype(np.int32)
     return [(k, ids[k:k + int(batch_pairs)]) for k in range(0, len(ids), int(batch_pairs))]
 
 

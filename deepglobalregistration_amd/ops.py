@@ -6,10 +6,19 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import check, get_ctx, ptr, stream_ptr, vp
 
 F32_EPS = float(np.finfo(np.float32).eps)
+
+_NP_PTR = {np.dtype(np.int32): _lib.c_i32p, np.dtype(np.int64): _lib.c_i64p, np.dtype(np.float32): _lib.c_f32p,
+           np.dtype(np.float64): _lib.c_f64p, np.dtype(np.uint8): C.POINTER(C.c_uint8)}
+
+
+def _np_ptr(a):
+    """Typed pointer to a contiguous host array of one of the dtypes the C ABI takes (None -> NULL); the pointer type
+    follows the array's own dtype, so the prototype refuses an array of the wrong one."""
+    return None if a is None else a.ctypes.data_as(_NP_PTR[a.dtype])
 
 
 def _dev(t):
@@ -277,47 +286,12 @@ class Maps:
 
 
 # ----------------------------------------------------------------------------
-def knn1(F0, F1, squared=False, return_distance=False):
-    lib = _lib.load()
-    dev = _dev(F0)
-    F0 = _as(F0, torch.float32, dev)
-    F1 = _as(F1, torch.float32, dev)
-    if F0.dim() != 2 or F1.dim() != 2 or F0.shape[1] != F1.shape[1]:
-        raise ValueError('F0 [N0,C] and F1 [N1,C] must share the feature width')
-    N0, N1 = F0.shape[0], F1.shape[0]
-    idx = torch.empty(N0, dtype=torch.int64, device=dev)
-    dist = torch.empty(N0, dtype=torch.float32, device=dev) if return_distance else None
-    check(lib.dgr_knn1_l2(get_ctx(dev), ptr(F0), N0, ptr(F1), N1, F0.shape[1], int(squared), ptr(idx),
-                          ptr(dist), stream_ptr(dev.index)))
-    return (idx, dist) if return_distance else idx
-
-
-def knn1_batch(F0, F1, off0, off1, squared=False, return_distance=False):
-    """1-NN of every pair (rows off0[p]:off0[p+1] of F0 against rows off1[p]:off1[p+1] of F1) in one library call;
-    indices address rows of the concatenated F1."""
-    lib = _lib.load()
-    dev = _dev(F0)
-    F0 = _as(F0, torch.float32, dev)
-    F1 = _as(F1, torch.float32, dev)
-    if F0.dim() != 2 or F1.dim() != 2 or F0.shape[1] != F1.shape[1]:
-        raise ValueError('F0 [N0,C] and F1 [N1,C] must share the feature width')
-    o0 = np.ascontiguousarray(off0, dtype=np.int64)
-    o1 = np.ascontiguousarray(off1, dtype=np.int64)
-    if len(o0) != len(o1) or len(o0) < 2 or o0[0] != 0 or o1[0] != 0 or o0[-1] != F0.shape[0] or o1[-1] != F1.shape[0]:
-        raise ValueError('off0 / off1 must be [npairs+1] row offsets covering F0 / F1')
-    idx = torch.empty(F0.shape[0], dtype=torch.int64, device=dev)
-    dist = torch.empty(F0.shape[0], dtype=torch.float32, device=dev) if return_distance else None
-    check(lib.dgr_knn1_l2_batch(get_ctx(dev), ptr(F0), o0.ctypes.data_as(_lib.c_i64p), ptr(F1),
-                                o1.ctypes.data_as(_lib.c_i64p), len(o0) - 1, F0.shape[1], int(squared), ptr(idx),
-                                ptr(dist), stream_ptr(dev.index)))
-    return (idx, dist) if return_distance else idx
-
-
 KNN_MAX_K = 32   # DGR_KNN_MAX_K of include/dgr_hip.h
 
 
 def check_knn_k(k):
     """The k of a k-NN search as an int in [1, KNN_MAX_K]; ValueError otherwise (before any device work)."""
+    # (not _args.integer: the range message prints int(k), the type message k itself)
     if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
         raise ValueError(f'knn must be an integer in [1, {KNN_MAX_K}], got {k!r}')
     if not 1 <= int(k) <= KNN_MAX_K:
@@ -325,10 +299,9 @@ def check_knn_k(k):
     return int(k)
 
 
-def knn(F0, F1, k, squared=False, return_distance=False):
-    """The k nearest rows of F1 for every row of F0: idx int64 [N0,k] (ascending distance, equal distances by the
-    smaller index, column 0 = knn1), dist f32 [N0,k]; columns j >= N1 hold index 0 and distance inf."""
-    k = check_knn_k(k)
+def _knn(F0, F1, off0, off1, k, squared, return_distance):
+    """The four k-NN searches.  off0 / off1 None: one pair (F0 against F1), otherwise the batched entry points; k None:
+    the 1-NN entry points, which write idx [N0] where the k-NN ones (k from `check_knn_k`) write [N0,k]."""
     lib = _lib.load()
     dev = _dev(F0)
     F0 = _as(F0, torch.float32, dev)
@@ -336,33 +309,43 @@ def knn(F0, F1, k, squared=False, return_distance=False):
     if F0.dim() != 2 or F1.dim() != 2 or F0.shape[1] != F1.shape[1]:
         raise ValueError('F0 [N0,C] and F1 [N1,C] must share the feature width')
     N0, N1 = F0.shape[0], F1.shape[0]
-    idx = torch.empty((N0, k), dtype=torch.int64, device=dev)
-    dist = torch.empty((N0, k), dtype=torch.float32, device=dev) if return_distance else None
-    check(lib.dgr_knn_l2(get_ctx(dev), ptr(F0), N0, ptr(F1), N1, F0.shape[1], k, int(squared), ptr(idx), ptr(dist),
-                         stream_ptr(dev.index)))
+    if off0 is None:
+        fn = lib.dgr_knn1_l2 if k is None else lib.dgr_knn_l2
+        sides = (ptr(F0), N0, ptr(F1), N1)
+    else:
+        o0 = np.ascontiguousarray(off0, dtype=np.int64)
+        o1 = np.ascontiguousarray(off1, dtype=np.int64)
+        if len(o0) != len(o1) or len(o0) < 2 or o0[0] != 0 or o1[0] != 0 or o0[-1] != N0 or o1[-1] != N1:
+            raise ValueError('off0 / off1 must be [npairs+1] row offsets covering F0 / F1')
+        fn = lib.dgr_knn1_l2_batch if k is None else lib.dgr_knn_l2_batch
+        sides = (ptr(F0), _np_ptr(o0), ptr(F1), _np_ptr(o1), len(o0) - 1)
+    idx = torch.empty(N0 if k is None else (N0, k), dtype=torch.int64, device=dev)
+    dist = torch.empty(idx.shape, dtype=torch.float32, device=dev) if return_distance else None
+    check(fn(get_ctx(dev), *sides, F0.shape[1], *(() if k is None else (k,)), int(squared), ptr(idx), ptr(dist),
+             stream_ptr(dev.index)))
     return (idx, dist) if return_distance else idx
+
+
+def knn1(F0, F1, squared=False, return_distance=False):
+    return _knn(F0, F1, None, None, None, squared, return_distance)
+
+
+def knn1_batch(F0, F1, off0, off1, squared=False, return_distance=False):
+    """1-NN of every pair (rows off0[p]:off0[p+1] of F0 against rows off1[p]:off1[p+1] of F1) in one library call;
+    indices address rows of the concatenated F1."""
+    return _knn(F0, F1, off0, off1, None, squared, return_distance)
+
+
+def knn(F0, F1, k, squared=False, return_distance=False):
+    """The k nearest rows of F1 for every row of F0: idx int64 [N0,k] (ascending distance, equal distances by the
+    smaller index, column 0 = knn1), dist f32 [N0,k]; columns j >= N1 hold index 0 and distance inf."""
+    return _knn(F0, F1, None, None, check_knn_k(k), squared, return_distance)
 
 
 def knn_batch(F0, F1, off0, off1, k, squared=False, return_distance=False):
     """k-NN of every pair (rows off0[p]:off0[p+1] of F0 against rows off1[p]:off1[p+1] of F1) in one library call:
     idx [off0[-1],k] addresses rows of the concatenated F1 (padding columns of pair p hold off1[p])."""
-    k = check_knn_k(k)
-    lib = _lib.load()
-    dev = _dev(F0)
-    F0 = _as(F0, torch.float32, dev)
-    F1 = _as(F1, torch.float32, dev)
-    if F0.dim() != 2 or F1.dim() != 2 or F0.shape[1] != F1.shape[1]:
-        raise ValueError('F0 [N0,C] and F1 [N1,C] must share the feature width')
-    o0 = np.ascontiguousarray(off0, dtype=np.int64)
-    o1 = np.ascontiguousarray(off1, dtype=np.int64)
-    if len(o0) != len(o1) or len(o0) < 2 or o0[0] != 0 or o1[0] != 0 or o0[-1] != F0.shape[0] or o1[-1] != F1.shape[0]:
-        raise ValueError('off0 / off1 must be [npairs+1] row offsets covering F0 / F1')
-    idx = torch.empty((F0.shape[0], k), dtype=torch.int64, device=dev)
-    dist = torch.empty((F0.shape[0], k), dtype=torch.float32, device=dev) if return_distance else None
-    check(lib.dgr_knn_l2_batch(get_ctx(dev), ptr(F0), o0.ctypes.data_as(_lib.c_i64p), ptr(F1),
-                               o1.ctypes.data_as(_lib.c_i64p), len(o0) - 1, F0.shape[1], k, int(squared), ptr(idx),
-                               ptr(dist), stream_ptr(dev.index)))
-    return (idx, dist) if return_distance else idx
+    return _knn(F0, F1, off0, off1, check_knn_k(k), squared, return_distance)
 
 
 KNN_TRACE_FIELDS = ('pair', 'table', 'route', 'fallback', 'list_len', 'redo', 'cand_max', 'cand_zero')
@@ -398,7 +381,7 @@ def knn_trace_rows(device):
     check(lib.dgr_debug_knn_trace(get_ctx(dev), None, 0, C.byref(n)))
     rows = np.zeros((n.value, len(KNN_TRACE_FIELDS)), np.int32)
     if n.value:
-        check(lib.dgr_debug_knn_trace(get_ctx(dev), rows.ctypes.data_as(_lib.c_i32p), n.value, C.byref(n)))
+        check(lib.dgr_debug_knn_trace(get_ctx(dev), _np_ptr(rows), n.value, C.byref(n)))
     return rows
 
 
@@ -549,41 +532,13 @@ def ransac_correspondence(X, Y, distance_threshold, num_hypotheses, seed=0):
 # ----------------------------------------------------------------------------
 # ground-truth matches and validation counts (csrc/gtmatch.hip).  Every argument check below runs on the host values
 # alone, BEFORE a tensor is moved or the library context is created.
-def _offsets(off, name, total=None):
-    o = np.ascontiguousarray(np.asarray(off), dtype=np.int64).reshape(-1)
-    if len(o) < 2 or o[0] != 0 or bool((np.diff(o) < 0).any()):
-        raise ValueError(f'{name} must be [npairs+1] row offsets that start at 0 and do not decrease')
-    if total is not None and o[-1] != total:
-        raise ValueError(f'{name} ends at {int(o[-1])}, the array has {int(total)} rows')
-    return o
-
-
-def _rows(a, width, name):
-    shape = tuple(a.shape) if hasattr(a, 'shape') else np.asarray(a).shape
-    if len(shape) != 2 or shape[1] != width:
-        raise ValueError(f'{name} must be [N,{width}], got {shape}')
-    return shape[0]
-
-
 def check_radius_args(radius, K, T, npairs):
     """(radius, K as the C ABI wants it, T float64 [npairs,16]); ValueError for a radius that is not a positive finite
     number, a K that is neither None nor an integer >= 1 (the reference slices idx[:K]), a T that is not [npairs,4,4]
     (or one [4,4] for one pair) of finite numbers."""
-    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, float, np.integer, np.floating)) \
-            or not np.isfinite(radius) or radius <= 0:
-        raise ValueError(f'radius must be a positive finite number, got {radius!r}')
-    if K is not None and (isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or K < 1
-                          or K > np.iinfo(np.int32).max):
-        raise ValueError(f'K must be None or an integer >= 1, got {K!r}')
-    T = T.detach().cpu().numpy() if torch.is_tensor(T) else np.asarray(T)
-    if T.shape == (4, 4) and npairs == 1:
-        T = T[None]
-    if T.shape != (npairs, 4, 4):
-        raise ValueError(f'T must be [{npairs},4,4], got {T.shape}')
-    T = np.ascontiguousarray(T, dtype=np.float64).reshape(npairs, 16)
-    if not np.isfinite(T).all():
-        raise ValueError('T must be finite')
-    return float(radius), 0 if K is None else int(K), T
+    radius = _args.positive_number(radius, 'radius')
+    K = 0 if K is None else _args.integer(K, 'K', lambda v: 1 <= v <= np.iinfo(np.int32).max, 'None or an integer >= 1')
+    return radius, K, _args.pose_stack(T, npairs, 'T', 4)
 
 
 def radius_pairs_batch(xyz0, off0, xyz1, off1, T, radius, K=None):
@@ -591,8 +546,8 @@ def radius_pairs_batch(xyz0, off0, xyz1, off1, T, radius, K=None):
     xyz0 under the pose T[p] against rows off1[p]:off1[p+1] of xyz1.  Returns (pairs int64 [P,2] on the device: pair-local
     (i, j) with |T x0[i] - x1[j]| < radius, by i and then by (distance, j), the first K of every i; pair_off int64 numpy
     [npairs+1]: pair p owns pairs[pair_off[p]:pair_off[p+1]])."""
-    n0, n1 = _rows(xyz0, 3, 'xyz0'), _rows(xyz1, 3, 'xyz1')
-    o0, o1 = _offsets(off0, 'off0', n0), _offsets(off1, 'off1', n1)
+    n0, n1 = _args.rows(xyz0, 3, 'xyz0'), _args.rows(xyz1, 3, 'xyz1')
+    o0, o1 = _args.pair_offsets(off0, 'off0', n0), _args.pair_offsets(off1, 'off1', n1)
     if len(o0) != len(o1):
         raise ValueError('off0 and off1 must describe the same number of pairs')
     npairs = len(o0) - 1
@@ -605,9 +560,8 @@ def radius_pairs_batch(xyz0, off0, xyz1, off1, T, radius, K=None):
     total = C.c_int64(0)
 
     def call(pairs, capacity):
-        check(lib.dgr_radius_pairs_batch(get_ctx(dev), ptr(xyz0), o0.ctypes.data_as(_lib.c_i64p), ptr(xyz1),
-                                         o1.ctypes.data_as(_lib.c_i64p), npairs, T.ctypes.data_as(_lib.c_f64p), radius, K,
-                                         ptr(counts), ptr(pairs), capacity, C.byref(total), stream_ptr(dev.index)))
+        check(lib.dgr_radius_pairs_batch(get_ctx(dev), ptr(xyz0), _np_ptr(o0), ptr(xyz1), _np_ptr(o1), npairs, _np_ptr(T),
+                                         radius, K, ptr(counts), ptr(pairs), capacity, C.byref(total), stream_ptr(dev.index)))
     call(None, 0)
     pairs = torch.empty((total.value, 2), dtype=torch.int64, device=dev)
     if total.value:
@@ -620,15 +574,15 @@ def radius_pairs_batch(xyz0, off0, xyz1, off1, T, radius, K=None):
 
 def radius_pairs(xyz0, xyz1, T, radius, K=None):
     """One pair: int64 [P,2] (i, j) with |T x0[i] - x1[j]| < radius, the reference's get_matching_indices order."""
-    return radius_pairs_batch(xyz0, [0, _rows(xyz0, 3, 'xyz0')], xyz1, [0, _rows(xyz1, 3, 'xyz1')], T, radius, K)[0]
+    return radius_pairs_batch(xyz0, [0, _args.rows(xyz0, 3, 'xyz0')], xyz1, [0, _args.rows(xyz1, 3, 'xyz1')], T, radius, K)[0]
 
 
 def pairs_isin(pos, pos_off, pred, pred_off, M):
     """Correctness label of every predicted pair (dgr_pairs_isin_batch): uint8 [Q] on the device, 1 where
     pred[:,0] + pred[:,1] * M[p] occurs among pos[:,0] + pos[:,1] * M[p] of the same batch entry p (wrapping int64).
     pos int64 [P,2], pred int64 [Q,2], pos_off / pred_off [npairs+1], M one integer per batch entry."""
-    P, Q = _rows(pos, 2, 'pos'), _rows(pred, 2, 'pred')
-    po, qo = _offsets(pos_off, 'pos_off', P), _offsets(pred_off, 'pred_off', Q)
+    P, Q = _args.rows(pos, 2, 'pos'), _args.rows(pred, 2, 'pred')
+    po, qo = _args.pair_offsets(pos_off, 'pos_off', P), _args.pair_offsets(pred_off, 'pred_off', Q)
     Ms = np.ascontiguousarray(np.asarray(M), dtype=np.int64).reshape(-1)
     if len(po) != len(qo) or len(Ms) != len(po) - 1:
         raise ValueError('pos_off, pred_off and M must describe the same number of pairs')
@@ -636,8 +590,7 @@ def pairs_isin(pos, pos_off, pred, pred_off, M):
     dev = _dev(pred)
     pos, pred = _as(pos, torch.int64, dev), _as(pred, torch.int64, dev)
     out = torch.empty(Q, dtype=torch.uint8, device=dev)
-    check(lib.dgr_pairs_isin_batch(get_ctx(dev), ptr(pos), po.ctypes.data_as(_lib.c_i64p), ptr(pred),
-                                   qo.ctypes.data_as(_lib.c_i64p), len(Ms), Ms.ctypes.data_as(_lib.c_i64p), ptr(out),
+    check(lib.dgr_pairs_isin_batch(get_ctx(dev), ptr(pos), _np_ptr(po), ptr(pred), _np_ptr(qo), len(Ms), _np_ptr(Ms), ptr(out),
                                    stream_ptr(dev.index)))
     return out
 
@@ -648,18 +601,16 @@ def validation_counts(label, weights, off, threshold=0.5):
     Q = int(label.shape[0]) if hasattr(label, 'shape') and len(label.shape) >= 1 else -1
     if Q < 0 or int(np.prod(tuple(label.shape))) != Q or int(np.prod(tuple(weights.shape))) != Q:
         raise ValueError('label and weights must hold one entry per predicted pair')
-    o = _offsets(off, 'off', Q)
-    if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)) \
-            or np.isnan(threshold):
+    o = _args.pair_offsets(off, 'off', Q)
+    if not _args.is_number(threshold) or np.isnan(threshold):   # (any number, +-inf too: not _args.positive_number)
         raise ValueError(f'threshold must be a number, got {threshold!r}')
     lib = _lib.load()
     dev = _dev(weights)
     label = _as(label, torch.uint8, dev).reshape(-1)
     weights = _as(weights, torch.float32, dev).reshape(-1)
     out = np.zeros((len(o) - 1, 6), np.int64)
-    check(lib.dgr_validation_counts(get_ctx(dev), ptr(label), ptr(weights), float(threshold),
-                                    o.ctypes.data_as(_lib.c_i64p), len(o) - 1, out.ctypes.data_as(_lib.c_i64p),
-                                    stream_ptr(dev.index)))
+    check(lib.dgr_validation_counts(get_ctx(dev), ptr(label), ptr(weights), float(threshold), _np_ptr(o), len(o) - 1,
+                                    _np_ptr(out), stream_ptr(dev.index)))
     return out
 
 
@@ -674,32 +625,10 @@ def check_score_args(n_rows, bank_off, pair_ids, T, radius):
     to the bank's `n_rows`, a pair list that is empty, not [n,2] integers or names a fragment outside the bank, a T that is
     not [n,4,4] (or one [4,4] for one pair) or has a non-finite entry in its first three rows, a radius that is not a
     positive finite number.  Pure host arithmetic: nothing touches the device."""
-    off = np.asarray(bank_off.cpu() if torch.is_tensor(bank_off) else bank_off)
-    if off.ndim != 1 or len(off) < 2 or not np.issubdtype(off.dtype, np.integer):
-        raise ValueError('bank_off must be a 1-D integer array [nfrag+1]')
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    if off[0] < 0 or bool((np.diff(off) <= 0).any()) or off[-1] != n_rows:
-        raise ValueError(f'bank_off must ascend strictly (no empty fragment) from >= 0 to the row count {int(n_rows)}')
-    ids = np.asarray(pair_ids.cpu() if torch.is_tensor(pair_ids) else pair_ids)
-    if ids.size == 0:
-        raise ValueError('the pair list is empty')
-    if ids.ndim != 2 or ids.shape[1] != 2 or not np.issubdtype(ids.dtype, np.integer):
-        raise ValueError('pair_ids must be an [n,2] integer array')
-    nfrag = len(off) - 1
-    if bool((ids < 0).any()) or bool((ids >= nfrag).any()):
-        raise ValueError(f'pair id outside [0, {nfrag})')
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    radius, _, _ = check_radius_args(radius, None, np.eye(4), 1)
-    n = len(ids)
-    T = T.detach().cpu().numpy() if torch.is_tensor(T) else np.asarray(T)
-    if T.shape == (4, 4) and n == 1:
-        T = T[None]
-    if T.shape != (n, 4, 4):
-        raise ValueError(f'T must be [{n},4,4], got {T.shape}')
-    T = np.ascontiguousarray(T, dtype=np.float64).reshape(n, 16)
-    if not np.isfinite(T[:, :12]).all():
-        raise ValueError('T must be finite (first three rows)')
-    return off, ids, T, radius
+    off = _args.fragment_offsets(bank_off, n_rows, 'bank_off')
+    ids = _args.pair_ids(pair_ids, len(off) - 1, 'pair_ids')
+    radius = _args.positive_number(radius, 'radius')
+    return off, ids, _args.pose_stack(T, len(ids), 'T', 3), radius
 
 
 def score_pairs(bank_xyz, bank_off, pair_ids, T, radius):
@@ -708,14 +637,13 @@ def score_pairs(bank_xyz, bank_off, pair_ids, T, radius):
     [n,11] = (n, sum d^2, sum q [3], sum qx qx, qx qy, qx qz, qy qy, qy qz, qz qz) with q the nearest such target row
     (ties: the smaller row).  bank_xyz [N,3] with fragment f in rows bank_off[f]:bank_off[f+1].
     `core.pair_score.scores_from_sums` turns the rows into fitness, inlier RMSE and the 6x6 information matrix."""
-    off, ids, T, radius = check_score_args(_rows(bank_xyz, 3, 'bank_xyz'), bank_off, pair_ids, T, radius)
+    off, ids, T, radius = check_score_args(_args.rows(bank_xyz, 3, 'bank_xyz'), bank_off, pair_ids, T, radius)
     lib = _lib.load()
     xyz = _xyz_dev(bank_xyz)
     dev = xyz.device
     out = np.zeros((len(ids), SCORE_WIDTH), np.float64)
-    check(lib.dgr_score_pairs(get_ctx(dev), ptr(xyz), off.ctypes.data_as(_lib.c_i64p), len(off) - 1,
-                              ids.ctypes.data_as(_lib.c_i32p), len(ids), T.ctypes.data_as(_lib.c_f64p), radius,
-                              out.ctypes.data_as(_lib.c_f64p), stream_ptr(dev.index)))
+    check(lib.dgr_score_pairs(get_ctx(dev), ptr(xyz), _np_ptr(off), len(off) - 1, _np_ptr(ids), len(ids), _np_ptr(T), radius,
+                              _np_ptr(out), stream_ptr(dev.index)))
     return out
 
 
@@ -736,25 +664,18 @@ def check_voxel_mean_args(xyz, voxel_size, off=None, frag_ids=None, T=None, orig
         raise ValueError('xyz must be a numpy array or a torch tensor')
     if str(xyz.dtype).replace('torch.', '') not in ('float32', 'float64'):
         raise ValueError(f'xyz must be float32 or float64, got {xyz.dtype}')
-    return check_voxel_mean_rows(_rows(xyz, 3, 'xyz'), voxel_size, off, frag_ids, T, origin)
+    return check_voxel_mean_rows(_args.rows(xyz, 3, 'xyz'), voxel_size, off, frag_ids, T, origin)
 
 
 def check_voxel_mean_rows(n_rows, voxel_size, off=None, frag_ids=None, T=None, origin=None):
     """`check_voxel_mean_args` behind the check of `xyz` itself, for a point array of `n_rows` rows."""
-    if isinstance(voxel_size, (bool, np.bool_)) or not isinstance(voxel_size, (int, float, np.integer, np.floating)) \
-            or not np.isfinite(voxel_size) or voxel_size <= 0:
-        raise ValueError(f'voxel_size must be a positive finite number, got {voxel_size!r}')
+    voxel_size = _args.positive_number(voxel_size, 'voxel_size')
     if off is None:
         if n_rows == 0:
             raise ValueError('empty point cloud')
         off = np.array([0, n_rows], np.int64)
     else:
-        off = np.asarray(off.cpu() if torch.is_tensor(off) else off)
-        if off.ndim != 1 or len(off) < 2 or not np.issubdtype(off.dtype, np.integer):
-            raise ValueError('off must be a 1-D integer array [nfrag+1]')
-        off = np.ascontiguousarray(off, dtype=np.int64)
-        if off[0] < 0 or bool((np.diff(off) <= 0).any()) or off[-1] != n_rows:
-            raise ValueError(f'off must ascend strictly (no empty fragment) from >= 0 to the row count {int(n_rows)}')
+        off = _args.fragment_offsets(off, n_rows, 'off')
     nfrag = len(off) - 1
     ids = None
     if frag_ids is not None:
@@ -774,16 +695,9 @@ def check_voxel_mean_rows(n_rows, voxel_size, off=None, frag_ids=None, T=None, o
         ids = np.ascontiguousarray(ids, dtype=np.int32)
     nsel = nfrag if ids is None else len(ids)
     if T is not None:
-        T = T.detach().cpu().numpy() if torch.is_tensor(T) else np.asarray(T)
-        if T.shape == (4, 4) and nsel == 1:
-            T = T[None]
-        if T.shape != (nsel, 4, 4):
-            raise ValueError(f'T must be [{nsel},4,4], got {T.shape}')
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(nsel, 16)
-        if not np.isfinite(T[:, :12]).all():
-            raise ValueError('T must be finite (first three rows)')
+        T = _args.pose_stack(T, nsel, 'T', 3)
     try:
-        origin = np.zeros(3) if origin is None else np.ascontiguousarray(_host(origin), dtype=np.float64)
+        origin = np.zeros(3) if origin is None else np.ascontiguousarray(_args.host(origin), dtype=np.float64)
     except (TypeError, ValueError):
         raise ValueError('origin must be three finite numbers') from None
     if origin.shape != (3,) or not np.isfinite(origin).all():
@@ -791,7 +705,7 @@ def check_voxel_mean_rows(n_rows, voxel_size, off=None, frag_ids=None, T=None, o
     rows = int(np.diff(off).sum() if ids is None else (off[ids.astype(np.int64) + 1] - off[ids]).sum())
     if rows >= 2 ** 31:
         raise ValueError(f'{rows} selected rows: 2^31 or more')
-    return off, ids, T, origin, float(voxel_size), rows
+    return off, ids, T, origin, voxel_size, rows
 
 
 def voxel_mean(xyz, voxel_size, off=None, frag_ids=None, T=None, origin=None, return_sums=False):
@@ -813,9 +727,8 @@ def voxel_mean(xyz, voxel_size, off=None, frag_ids=None, T=None, origin=None, re
     sums = torch.empty((rows, 3), dtype=torch.int64, device=dev) if return_sums else None
     mean = torch.empty((rows, 3), dtype=torch.float64, device=dev)
     n, dropped = C.c_int64(0), C.c_int64(0)
-    check(lib.dgr_voxel_mean(get_ctx(dev), ptr(t), int(t.dtype == torch.float64), off.ctypes.data_as(_lib.c_i64p), len(off) - 1,
-                             None if ids is None else ids.ctypes.data_as(_lib.c_i32p), len(off) - 1 if ids is None else len(ids),
-                             None if T is None else T.ctypes.data_as(_lib.c_f64p), origin.ctypes.data_as(_lib.c_f64p),
+    check(lib.dgr_voxel_mean(get_ctx(dev), ptr(t), int(t.dtype == torch.float64), _np_ptr(off), len(off) - 1,
+                             _np_ptr(ids), len(off) - 1 if ids is None else len(ids), _np_ptr(T), _np_ptr(origin),
                              voxel_size, ptr(first), ptr(coords), ptr(count), ptr(sums), ptr(mean), C.byref(n),
                              C.byref(dropped), stream_ptr(dev.index)))
     V = n.value
@@ -846,36 +759,26 @@ def check_tsdf_args(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale
     if depth.ndim != 3 or min(depth.shape) < 1:
         raise ValueError(f'depth must be [F,H,W] with F, H, W >= 1, got {tuple(depth.shape)}')
     F, H, W = (int(v) for v in depth.shape)
-
-    def number(v, name):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) \
-                or not np.isfinite(v) or v <= 0:
-            raise ValueError(f'{name} must be a positive finite number, got {v!r}')
-        return float(v)
-
-    def integer(v, name, ok, what):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not ok(v):
-            raise ValueError(f'{name} must be {what}, got {v!r}')
-        return int(v)
-    voxel_length = number(voxel_length, 'voxel_length')
-    sdf_trunc = number(sdf_trunc, 'sdf_trunc')
-    depth_scale = number(depth_scale, 'depth_scale')
-    depth_trunc = number(depth_trunc, 'depth_trunc')
-    block = integer(block, 'block', lambda v: v in (8, 16), '8 or 16')
-    stride = integer(stride, 'stride', lambda v: v >= 1, 'an integer >= 1')
-    min_weight = integer(min_weight, 'min_weight', lambda v: 1 <= v < 2 ** 31, 'an integer >= 1')
+    voxel_length = _args.positive_number(voxel_length, 'voxel_length')
+    sdf_trunc = _args.positive_number(sdf_trunc, 'sdf_trunc')
+    depth_scale = _args.positive_number(depth_scale, 'depth_scale')
+    depth_trunc = _args.positive_number(depth_trunc, 'depth_trunc')
+    block = _args.integer(block, 'block', lambda v: v in (8, 16), '8 or 16')
+    stride = _args.integer(stride, 'stride', lambda v: v >= 1, 'an integer >= 1')
+    min_weight = _args.integer(min_weight, 'min_weight', lambda v: 1 <= v < 2 ** 31, 'an integer >= 1')
     if sdf_trunc > voxel_length * block:
         raise ValueError(f'sdf_trunc {sdf_trunc} exceeds a block ({voxel_length} x {block}): a pixel would touch more than '
                          f'two blocks per axis')
     try:
-        intrinsic = np.ascontiguousarray(_host(intrinsic), dtype=np.float64)
+        intrinsic = np.ascontiguousarray(_args.host(intrinsic), dtype=np.float64)
     except (TypeError, ValueError):
         raise ValueError('intrinsic must be four finite numbers (fx, fy, cx, cy)') from None
     if intrinsic.shape != (4,) or not np.isfinite(intrinsic).all():
         raise ValueError('intrinsic must be four finite numbers (fx, fy, cx, cy)')
     if intrinsic[0] <= 0 or intrinsic[1] <= 0:
         raise ValueError('fx and fy must be positive')
-    pose = _host(pose)
+    # (not _args.pose_stack: a pose is inverted below, so its dtype is checked too and it stays [F,4,4])
+    pose = _args.host(pose)
     if pose.shape == (4, 4) and F == 1:
         pose = pose[None]
     if pose.shape != (F, 4, 4) or pose.dtype.kind not in 'fiu':
@@ -927,8 +830,7 @@ def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1
             blocks = torch.empty((max_blocks, 3), dtype=torch.int32, device=dev)
             tsdf = torch.empty((max_blocks, V), dtype=torch.float32, device=dev)
             weight = torch.empty((max_blocks, V), dtype=torch.int32, device=dev)
-        rc = lib.dgr_tsdf_fragment(get_ctx(dev), ptr(d), F, H, W, intrinsic.ctypes.data_as(_lib.c_f64p),
-                                   pose.ctypes.data_as(_lib.c_f64p), extrinsic.ctypes.data_as(_lib.c_f64p),
+        rc = lib.dgr_tsdf_fragment(get_ctx(dev), ptr(d), F, H, W, _np_ptr(intrinsic), _np_ptr(pose), _np_ptr(extrinsic),
                                    float(voxel_length), float(sdf_trunc), float(depth_scale), float(depth_trunc), int(block),
                                    int(stride), int(min_weight), ptr(xyz), max_points, ptr(blocks), ptr(tsdf), ptr(weight),
                                    max_blocks if return_volume else 0, C.byref(nb), C.byref(npts),
@@ -960,19 +862,9 @@ def check_tsdf_mesh_args(blocks, tsdf, weight, voxel_length, block=16, min_weigh
     are not on one GPU, a `blocks` that is not int32 [nb,3], a `tsdf` that is not float32 [nb, block^3], a `weight` that is
     not int32 of `tsdf`'s shape, a `block` other than 8 or 16, a `voxel_length` that is not a positive finite number,
     `min_weight` < 1, 5 nb block^3 >= 2^31.  Nothing touches the device (block coordinates are checked there)."""
-    def number(v, name):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) \
-                or not np.isfinite(v) or v <= 0:
-            raise ValueError(f'{name} must be a positive finite number, got {v!r}')
-        return float(v)
-
-    def integer(v, name, ok, what):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not ok(v):
-            raise ValueError(f'{name} must be {what}, got {v!r}')
-        return int(v)
-    voxel_length = number(voxel_length, 'voxel_length')
-    block = integer(block, 'block', lambda v: v in (8, 16), '8 or 16')
-    min_weight = integer(min_weight, 'min_weight', lambda v: 1 <= v < 2 ** 31, 'an integer >= 1')
+    voxel_length = _args.positive_number(voxel_length, 'voxel_length')
+    block = _args.integer(block, 'block', lambda v: v in (8, 16), '8 or 16')
+    min_weight = _args.integer(min_weight, 'min_weight', lambda v: 1 <= v < 2 ** 31, 'an integer >= 1')
     for t, name in ((blocks, 'blocks'), (tsdf, 'tsdf'), (weight, 'weight')):
         if not torch.is_tensor(t) or not t.is_cuda:
             raise ValueError(f'{name} must be a tensor on the GPU')
@@ -1026,10 +918,6 @@ def tsdf_mesh(blocks, tsdf, weight, voxel_length, block=16, min_weight=1, normal
 PG_MAX_NODES = 128   # DGR_PG_MAX_NODES
 
 
-def _host(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-
-
 def check_pose_graph_args(node_off, edge_off, edge_ids, edge_T, edge_info, edge_uncertain, pose_init, params):
     """The arguments of `pose_graph_optimize` as the C ABI wants them: (node_off int64 [g+1], edge_off int64 [g+1],
     ids int32 [E,2], X float64 [E,16], info float64 [E,36], uncertain uint8 [E], poses float64 [N,16], params: one
@@ -1039,8 +927,8 @@ def check_pose_graph_args(node_off, edge_off, edge_ids, edge_T, edge_info, edge_
     node to itself, a non-finite X, information matrix or initial pose, mu <= 0, a reference node outside the graph, a
     negative max_iter or rel_tol, arrays whose shapes do not fit.  Pure host arithmetic: nothing touches the device."""
     offs = []
-    for name, o in (('node_off', node_off), ('edge_off', edge_off)):
-        o = _host(o)
+    for name, o in (('node_off', node_off), ('edge_off', edge_off)):   # (from 0 exactly, and other words than a bank's)
+        o = _args.host(o)
         if o.ndim != 1 or len(o) < 2 or not np.issubdtype(o.dtype, np.integer):
             raise ValueError(f'{name} must be a 1-D integer array [ngraphs+1]')
         o = np.ascontiguousarray(o, dtype=np.int64)
@@ -1055,7 +943,7 @@ def check_pose_graph_args(node_off, edge_off, edge_ids, edge_T, edge_info, edge_
     if bool((n_of > PG_MAX_NODES).any()):
         raise ValueError(f'a graph has {int(n_of.max())} nodes: at most {PG_MAX_NODES} (6 (n - 1) = 762 unknowns and a '
                          '4.6 MB normal matrix per graph)')
-    ids = _host(edge_ids)
+    ids = _args.host(edge_ids)
     if ids.shape != (E, 2) or not np.issubdtype(ids.dtype, np.integer):
         raise ValueError(f'edge_ids must be an [{E},2] integer array')
     n_edge = np.repeat(n_of, np.diff(eoff))
@@ -1065,8 +953,8 @@ def check_pose_graph_args(node_off, edge_off, edge_ids, edge_T, edge_info, edge_
         raise ValueError('an edge joins a node to itself')
     ids = np.ascontiguousarray(ids, dtype=np.int32)
 
-    def mats(a, k, n, name):
-        a = _host(a)
+    def mats(a, k, n, name):   # (not _args.pose_stack: 6x6 too, and one matrix does not stand for a stack of one)
+        a = _args.host(a)
         if a.shape != (n, k, k):
             raise ValueError(f'{name} must be [{n},{k},{k}], got {a.shape}')
         a = np.ascontiguousarray(a, dtype=np.float64).reshape(n, k * k)
@@ -1074,7 +962,7 @@ def check_pose_graph_args(node_off, edge_off, edge_ids, edge_T, edge_info, edge_
             raise ValueError(f'{name} must be finite')
         return a
     X, info, poses = mats(edge_T, 4, E, 'edge_T'), mats(edge_info, 6, E, 'edge_info'), mats(pose_init, 4, N, 'pose_init')
-    unc = _host(edge_uncertain)
+    unc = _args.host(edge_uncertain)
     if unc.shape != (E,):
         raise ValueError(f'edge_uncertain must be [{E}]')
     unc = np.ascontiguousarray(unc.astype(bool), dtype=np.uint8)
@@ -1115,16 +1003,53 @@ def pose_graph_optimize(node_off, edge_off, edge_ids, edge_T, edge_info, edge_un
     cp = (_lib.PgParams * ng)(*[_lib.PgParams(*p) for p in prm])
     pose_out, line, stats = np.zeros_like(poses), np.zeros(len(ids)), np.zeros((ng, 4))
     with torch.cuda.device(dev):
-        check(lib.dgr_pose_graph_optimize(get_ctx(dev), ng, noff.ctypes.data_as(_lib.c_i64p), eoff.ctypes.data_as(_lib.c_i64p),
-                                          ids.ctypes.data_as(_lib.c_i32p), X.ctypes.data_as(_lib.c_f64p),
-                                          info.ctypes.data_as(_lib.c_f64p), unc.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                          poses.ctypes.data_as(_lib.c_f64p), cp, pose_out.ctypes.data_as(_lib.c_f64p),
-                                          line.ctypes.data_as(_lib.c_f64p), stats.ctypes.data_as(_lib.c_f64p),
-                                          stream_ptr(dev.index)))
+        check(lib.dgr_pose_graph_optimize(get_ctx(dev), ng, _np_ptr(noff), _np_ptr(eoff), _np_ptr(ids), _np_ptr(X),
+                                          _np_ptr(info), _np_ptr(unc), _np_ptr(poses), cp, _np_ptr(pose_out), _np_ptr(line),
+                                          _np_ptr(stats), stream_ptr(dev.index)))
     return pose_out.reshape(-1, 4, 4), line, stats
 
 
 # ----------------------------------------------------------------------------
+# what the two entry points of the fused pipeline share: the parameter record, the two test hooks, the outputs
+def _register_params(voxel_size, clip_weight_thresh, inlier_feature_type, max_iter, max_break_count, break_threshold_ratio,
+                     skip_refinement, safeguard, use_icp, ransac_hypotheses, ransac_seed):
+    return _lib.Params(float(clip_weight_thresh), float(voxel_size),
+                       {'ones': 0, 'coords': 1}[inlier_feature_type], int(max_iter), int(max_break_count),
+                       float(break_threshold_ratio), int(bool(skip_refinement)), int(bool(safeguard)),
+                       int(ransac_hypotheses), int(ransac_seed) & 0xffffffff, int(bool(use_icp)))
+
+
+def _register_out(npairs):
+    """(T float32 [npairs,16] -- float64 comes through `_register_T64` --, status int32 [npairs], stats float32 [npairs,4])"""
+    return np.empty((npairs, 16), np.float32), np.empty(npairs, np.int32), np.empty((npairs, 4), np.float32)
+
+
+def _register_hooks(forced_logit, override_idx1, n0, dev):
+    """(forced_logit f32, override_idx1 int64), each flat on `dev` or None; one given must hold `n0` entries, the rows of
+    the batch's concatenated fragment 0 (n0 None: the count is not known and not checked)."""
+    out = []
+    for t, dtype, name in ((forced_logit, torch.float32, 'forced_logit'), (override_idx1, torch.int64, 'override_idx1')):
+        if t is not None:
+            t = _as(t, dtype, dev).reshape(-1)
+            if n0 is not None and t.shape[0] != n0:
+                raise ValueError(f'{name} must have one entry per row of fragment 0')
+        out.append(t)
+    return out
+
+
+def _register_T64(lib, dev, npairs):
+    """T float64 [npairs,4,4] of the call that just returned: always at full width, whatever the flags (the RANSAC / ICP
+    stages compute in float64 like Open3D; without them the f32 estimate widens exactly): one return dtype.  The library
+    clears its float64 copy when a call starts, so a call that failed midway cannot leave an earlier batch's transforms
+    to be read here."""
+    T64 = np.empty((npairs, 16), np.float64)
+    n = C.c_int64(0)
+    check(lib.dgr_register_batch_f64(get_ctx(dev), _np_ptr(T64), npairs, C.byref(n)))
+    if n.value != npairs:
+        raise RuntimeError(f'dgr_register_batch_f64 holds {n.value} pairs, expected {npairs}')
+    return T64.reshape(npairs, 4, 4)
+
+
 def register_batch(fcgf, inlier, coords0, xyz0, off0, coords1, xyz1, off1, voxel_size,
                    clip_weight_thresh=0.05, inlier_feature_type='coords', max_iter=1000,
                    max_break_count=20, break_threshold_ratio=1e-4, skip_refinement=False,
@@ -1146,36 +1071,14 @@ def register_batch(fcgf, inlier, coords0, xyz0, off0, coords1, xyz1, off1, voxel
     o1 = (C.c_int64 * (npairs + 1))(*[int(v) for v in off1])
     if coords0.shape[0] != off0[-1] or coords1.shape[0] != off1[-1]:
         raise ValueError('offset arrays do not match the coordinate arrays')
-    prm = _lib.Params(float(clip_weight_thresh), float(voxel_size),
-                      {'ones': 0, 'coords': 1}[inlier_feature_type], int(max_iter), int(max_break_count),
-                      float(break_threshold_ratio), int(bool(skip_refinement)), int(bool(safeguard)),
-                      int(ransac_hypotheses), int(ransac_seed) & 0xffffffff, int(bool(use_icp)))
-    T = np.empty((npairs, 16), np.float32)   # (float32 at this entry point; float64 through dgr_register_batch_f64 below)
-    status = np.empty(npairs, np.int32)
-    stats = np.empty((npairs, 4), np.float32)
-    fl = None
-    if forced_logit is not None:
-        fl = _as(forced_logit, torch.float32, dev).reshape(-1)
-        if fl.shape[0] != coords0.shape[0]:
-            raise ValueError('forced_logit must have one entry per row of fragment 0')
-    ov = None
-    if override_idx1 is not None:
-        ov = _as(override_idx1, torch.int64, dev).reshape(-1)
-        if ov.shape[0] != coords0.shape[0]:
-            raise ValueError('override_idx1 must have one entry per row of fragment 0')
+    prm = _register_params(voxel_size, clip_weight_thresh, inlier_feature_type, max_iter, max_break_count,
+                           break_threshold_ratio, skip_refinement, safeguard, use_icp, ransac_hypotheses, ransac_seed)
+    T, status, stats = _register_out(npairs)
+    fl, ov = _register_hooks(forced_logit, override_idx1, coords0.shape[0], dev)
     check(lib.dgr_register_batch(get_ctx(dev), fcgf.handle, inlier.handle, ptr(coords0), ptr(xyz0), o0,
                                  ptr(coords1), ptr(xyz1), o1, npairs, C.byref(prm), ptr(ov), ptr(fl),
-                                 T.ctypes.data_as(_lib.c_f32p), status.ctypes.data_as(_lib.c_i32p),
-                                 stats.ctypes.data_as(_lib.c_f32p), stream_ptr(dev.index)))
-    # always at full width, whatever the flags (the RANSAC / ICP stages compute in float64 like Open3D; without them the
-    # f32 estimate widens exactly): one return dtype.  The library clears its float64 copy when a call starts, so a call
-    # that failed midway cannot leave an earlier batch's transforms to be read here.
-    T64 = np.empty((npairs, 16), np.float64)
-    n = C.c_int64(0)
-    check(lib.dgr_register_batch_f64(get_ctx(dev), T64.ctypes.data_as(_lib.c_f64p), npairs, C.byref(n)))
-    if n.value != npairs:
-        raise RuntimeError(f'dgr_register_batch_f64 holds {n.value} pairs, expected {npairs}')
-    return T64.reshape(npairs, 4, 4), status, stats
+                                 _np_ptr(T), _np_ptr(status), _np_ptr(stats), stream_ptr(dev.index)))
+    return _register_T64(lib, dev, npairs), status, stats
 
 
 def register_pairs(inlier, bank_coords, bank_xyz, bank_F, bank_off, pair_ids, voxel_size,
@@ -1201,36 +1104,16 @@ def register_pairs(inlier, bank_coords, bank_xyz, bank_F, bank_off, pair_ids, vo
     if nfrag < 1 or bank_coords.shape[0] != off[-1] or bank_xyz.shape[0] != off[-1] or bank_F.shape[0] != off[-1] \
             or bank_F.dim() != 2:
         raise ValueError('offset array does not match the bank arrays')
-    prm = _lib.Params(float(clip_weight_thresh), float(voxel_size),
-                      {'ones': 0, 'coords': 1}[inlier_feature_type], int(max_iter), int(max_break_count),
-                      float(break_threshold_ratio), int(bool(skip_refinement)), int(bool(safeguard)),
-                      int(ransac_hypotheses), int(ransac_seed) & 0xffffffff, int(bool(use_icp)))
-    T = np.empty((npairs, 16), np.float32)
-    status = np.empty(npairs, np.int32)
-    stats = np.empty((npairs, 4), np.float32)
+    prm = _register_params(voxel_size, clip_weight_thresh, inlier_feature_type, max_iter, max_break_count,
+                           break_threshold_ratio, skip_refinement, safeguard, use_icp, ransac_hypotheses, ransac_seed)
+    T, status, stats = _register_out(npairs)
     in_range = bool(((ids >= 0) & (ids < nfrag)).all())      # (out-of-range ids are the library's to report)
-    n0 = int((off[ids[:, 0] + 1] - off[ids[:, 0]]).sum()) if in_range else -1
-    fl = None
-    if forced_logit is not None:
-        fl = _as(forced_logit, torch.float32, dev).reshape(-1)
-        if in_range and fl.shape[0] != n0:
-            raise ValueError('forced_logit must have one entry per row of fragment 0')
-    ov = None
-    if override_idx1 is not None:
-        ov = _as(override_idx1, torch.int64, dev).reshape(-1)
-        if in_range and ov.shape[0] != n0:
-            raise ValueError('override_idx1 must have one entry per row of fragment 0')
+    n0 = int((off[ids[:, 0] + 1] - off[ids[:, 0]]).sum()) if in_range else None
+    fl, ov = _register_hooks(forced_logit, override_idx1, n0, dev)
     check(lib.dgr_register_pairs(get_ctx(dev), inlier.handle, ptr(bank_coords), ptr(bank_xyz), ptr(bank_F),
-                                 off.ctypes.data_as(_lib.c_i64p), nfrag, int(bank_F.shape[1]),
-                                 ids.ctypes.data_as(_lib.c_i32p), npairs, C.byref(prm), ptr(ov), ptr(fl),
-                                 T.ctypes.data_as(_lib.c_f32p), status.ctypes.data_as(_lib.c_i32p),
-                                 stats.ctypes.data_as(_lib.c_f32p), stream_ptr(dev.index)))
-    T64 = np.empty((npairs, 16), np.float64)   # (see register_batch)
-    n = C.c_int64(0)
-    check(lib.dgr_register_batch_f64(get_ctx(dev), T64.ctypes.data_as(_lib.c_f64p), npairs, C.byref(n)))
-    if n.value != npairs:
-        raise RuntimeError(f'dgr_register_batch_f64 holds {n.value} pairs, expected {npairs}')
-    return T64.reshape(npairs, 4, 4), status, stats
+                                 _np_ptr(off), nfrag, int(bank_F.shape[1]), _np_ptr(ids), npairs, C.byref(prm), ptr(ov),
+                                 ptr(fl), _np_ptr(T), _np_ptr(status), _np_ptr(stats), stream_ptr(dev.index)))
+    return _register_T64(lib, dev, npairs), status, stats
 
 
 _BATCH_OUT = {'idx1': (0, torch.int64), 'logit': (1, torch.float32), 'weights': (2, torch.float32),
