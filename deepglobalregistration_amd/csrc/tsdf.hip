@@ -127,7 +127,10 @@ __global__ void __launch_bounds__(TS_THREADS)
 // Cull: per chunk of 256 frames, thread t decides for frame t whether ANY voxel centre of the block can be updated: the
 // centres lie in a ball of radius sqrt(3)/2 bl around the block's centre, and an update needs z > 0, z < depth_trunc +
 // sdf_trunc (sdf > -trunc with m >= 1 and d <= depth_trunc) and a projection inside the image, i.e. the centre on the inner
-// side of the four planes through the camera that bound [0, W) x [0, H) in (uf, vf).  A frame is skipped only if the ball
+// side of the four planes through the camera that bound [0, W) x [0, H) in (uf, vf).  The test runs in camera coordinates,
+// where the ball's image lies within (largest row norm of the extrinsic's 3x3 part) x the world radius of the centre's image:
+// the radius term is stretched by max(1, that norm) -- 1 for a rigid pose, whatever an accepted pose that scales or shears
+// needs.  A frame is skipped only if the ball
 // lies outside one of these half-spaces by a margin of 1 % of the radius + 1e-6 + 1e-9 |centre|, orders of magnitude above
 // the rounding of either side; the bitwise comparison with the uncalled statement is the proof that nothing is lost.
 // workgroups per block: TsdfSplit (tsdf_common.h)
@@ -169,7 +172,11 @@ __global__ void __launch_bounds__(TS_THREADS)
         const double px = E[0] * ccx + E[1] * ccy + E[2] * ccz + E[3];
         const double py = E[4] * ccx + E[5] * ccy + E[6] * ccz + E[7];
         const double pz = E[8] * ccx + E[9] * ccy + E[10] * ccz + E[11];
-        const double mg = margin + 1e-9 * (fabs(px) + fabs(py) + fabs(pz));
+        // the ball in camera coordinates: coordinate r of E (c' - c) is at most |row r of E's 3x3 part| |c' - c|
+        const double n0 = E[0] * E[0] + E[1] * E[1] + E[2] * E[2], n1 = E[4] * E[4] + E[5] * E[5] + E[6] * E[6];
+        const double n2 = E[8] * E[8] + E[9] * E[9] + E[10] * E[10];
+        const double stretch = fmax(1.0, sqrt(fmax(fmax(n0, n1), n2)));
+        const double mg = margin * stretch + 1e-9 * (fabs(px) + fabs(py) + fabs(pz));
         const double l = cam.cx + 0.5, rr = Wd - cam.cx - 0.5, tt = cam.cy + 0.5, bb = Hd - cam.cy - 0.5;
         k = pz > -mg && pz - mg < cam.depth_trunc + cam.trunc
             && cam.fx * px + l * pz >= -mg * (cam.fx + fabs(l)) && cam.fx * px - rr * pz <= mg * (cam.fx + fabs(rr))

@@ -802,7 +802,8 @@ def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1
     """TSDF fusion of F depth frames under their camera poses and the surface points of the fused volume
     (dgr_tsdf_fragment; what the reference's util/integration.py does with Open3D's ScalableTSDFVolume).  depth uint16
     [F,H,W] (numpy or a device tensor), intrinsic = (fx, fy, cx, cy), pose [F,4,4] float64 camera-to-world as the
-    `.pose.txt` files give it; `extrinsic = inv(pose)` is taken here, on the host.  Blocks of `block`^3 voxels of
+    `.pose.txt` files give it; `extrinsic = inv(pose)` is taken here, on the host (any finite, invertible pose: it need
+    not be rigid).  Blocks of `block`^3 voxels of
     `voxel_length` are allocated where the pixels on a grid of `stride` see a surface, within `sdf_trunc` of it; every
     voxel of these blocks is integrated over all frames in order; the points are the zero crossings on the voxels' +x,
     +y, +z edges whose two ends have at least `min_weight` observations.

@@ -554,7 +554,12 @@ int dgr_voxel_mean(dgr_ctx *ctx, const void *xyz, int is_f64, const int64_t *off
  * [max_blocks, block^3], weight_out dev i32 [max_blocks, block^3]: all three or none (NULL); without them the volume lives in
  * the context's workspace.  *n_blocks_out, *n_points_out HOST: the two values the call synchronises for; *kept_out HOST
  * (NULL: not counted): the (block, frame) pairs the integration did not cull -- a frame is skipped for a whole block only
- * when no voxel of the block can pass the tests above, so the cull does not reach the result.
+ * when no voxel of the block can pass the tests above, so the cull does not reach the result: the voxel centres lie in a
+ * ball of radius sqrt(3)/2 bl around the block's centre, which extrinsic_f maps into a ball of at most max(1, the largest
+ * Euclidean norm of a row of extrinsic_f's 3x3 part) times that radius around the mapped centre, and the frame is skipped
+ * only when THAT ball (plus 1 % and a rounding allowance) lies wholly outside z > 0, z < depth_trunc + sdf_trunc or one of
+ * the four planes through the camera that bound the image.  Poses need not be rigid: any finite pose whose inverse the
+ * caller could form is accepted (scale, shear, a rotation rounded to fewer digits), and the statement holds for all of them.
  * No floating-point atomics: a voxel belongs to one thread and output positions come from scans; two runs agree bit for bit.
  * DGR_ENOMEM: the workspace cannot be grown, more blocks than max_blocks (reported before the integration) or more points
  * than max_points (nothing is written to xyz_out) -- *n_blocks_out / *n_points_out then hold what is needed; 2^31 or more

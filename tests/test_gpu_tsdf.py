@@ -11,34 +11,9 @@ import torch
 
 import tsdf_cases
 import tsdf_ref
+from tsdf_checks import check as _check, run as _run, same as _same
 
 pytestmark = pytest.mark.gpu
-
-
-def _run(depth, K, poses, voxel, trunc, **kw):
-    from deepglobalregistration_amd import ops
-    r = ops.tsdf_fragment(depth, K, poses, voxel, trunc, return_volume=True, **kw)
-    assert r['xyz'].is_cuda and r['xyz'].dtype == torch.float64 and r['blocks'].dtype == torch.int32
-    assert r['tsdf'].dtype == torch.float32 and r['weight'].dtype == torch.int32
-    B = kw.get('block', 16)
-    assert r['xyz'].shape[1:] == (3,) and r['blocks'].shape[1:] == (3,)
-    assert r['tsdf'].shape == (len(r['blocks']), B ** 3) and r['weight'].shape == r['tsdf'].shape
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
-def _same(got, want, what=''):
-    for k, bits in (('blocks', np.int32), ('weight', np.int32), ('tsdf', np.int32), ('xyz', np.int64)):
-        g, w = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
-        assert g.shape == w.shape and g.dtype == w.dtype, f'{what}: {k} is {g.dtype}{g.shape}, statement {w.dtype}{w.shape}'
-        bad = np.nonzero((g.view(bits) != w.view(bits)).reshape(len(g), int(np.prod(g.shape[1:]))).any(1))[0]
-        assert len(bad) == 0, f'{what}: {k} differs in {len(bad)} of {len(g)} rows, first {bad[0]}: {g[bad[0]]} / {w[bad[0]]}'
-
-
-def _check(depth, K, poses, voxel, trunc, what='', **kw):
-    got = _run(depth, K, poses, voxel, trunc, **kw)
-    want = tsdf_ref.tsdf_fragment(depth, K, poses, voxel, trunc, **kw)
-    _same(got, want, what)
-    return got
 
 
 def _small():

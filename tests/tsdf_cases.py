@@ -1,6 +1,8 @@
 """The synthetic depth sequences the TSDF tests share, and their numpy statements, each computed once per session."""
 import functools
 
+import numpy as np
+
 from deepglobalregistration_amd import synth
 import tsdf_ref
 
@@ -28,3 +30,85 @@ def statement(size, seed=0, block=16, stride=4, min_weight=1):
     for a in out.values():
         a.setflags(write=False)
     return out
+
+
+# ---- the edges (tests/test_gpu_tsdf_edges.py; their premises in tests/test_tsdf_cpu.py) ----------------------------------
+FRAME_CHUNK = 256   # TS_THREADS of csrc/tsdf.hip: the cull decides 256 frames at a time
+SHEAR = ((1.0, 0.8, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+# name -> (3x3 matrix the rows 0..2 of every pose are premultiplied by, factor on voxel_length and sdf_trunc)
+NON_RIGID = {'half': (np.eye(3) * 0.5, 0.5), 'quarter': (np.eye(3) * 0.25, 0.25), 'double': (np.eye(3) * 2.0, 2.0),
+             'squeeze_x': (np.diag([0.4, 1.0, 1.0]), 1.0), 'squeeze_z': (np.diag([1.0, 1.0, 0.4]), 1.0),
+             'shear': (np.array(SHEAR), 1.0)}
+INTRINSICS = {'fx_ne_fy': (70.0, 45.0, 39.5, 29.5), 'cx_left_of_image': (70.0, 70.0, -10.0, 29.5),
+              'cy_below_image': (70.0, 70.0, 39.5, 75.0), 'all_at_once': (35.0, 90.0, 3.0, 50.0)}
+FRAMES = {'frames255': 255, 'frames256': 256, 'frames257': 257, 'frames513': 513}
+LIMIT = {'limit_plus_x': (0, 1), 'limit_minus_x': (0, -1), 'limit_plus_z': (2, 1), 'limit_minus_z': (2, -1)}
+SHAPES = ('one_row', 'one_column', 'one_pixel', 'stride_beyond_image', 'one_frame')
+EDGE_CASES = tuple(FRAMES) + ('frames257_reversed',) + tuple(NON_RIGID) + ('rotation_rounded_to_float32',) + tuple(LIMIT) \
+    + ('beyond_limit',) + tuple(INTRINSICS) + SHAPES
+
+# (block, frame) pairs `ts_integrate` keeps for the rigid fixtures, measured once on an MI355X BEFORE the cull's radius was
+# stretched by the extrinsic's row norm: (size, block, stride) -> kept.  The stretch is exactly 1 for them and must stay so.
+RIGID_KEPT = {('small', 8, 1): 283, ('small', 8, 4): 278, ('small', 16, 1): 62, ('small', 16, 4): 62,
+              ('large', 8, 1): 1928, ('large', 8, 4): 1882, ('large', 16, 1): 357, ('large', 16, 4): 341}
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(name, block):
+    """dict(depth, K, poses, voxel, trunc, stride) of one named edge; only the block limit's cases depend on `block`"""
+    depth, K, poses, _ = sequence('small')
+    voxel, trunc, stride = 0.04, 0.16, 4
+    if name in FRAMES or name == 'frames257_reversed':
+        depth, K, poses, _ = synth.synth_rgbd(0, FRAMES.get(name, 257), 20, 15, 17.5, sweep_deg=120.0)
+        stride = 1
+        if name == 'frames257_reversed':
+            depth, poses = depth[::-1], poses[::-1]
+    elif name in NON_RIGID:
+        A, s = NON_RIGID[name]
+        poses = poses.copy()
+        poses[:, :3, :] = A @ poses[:, :3, :]
+        voxel, trunc = voxel * s, trunc * s
+    elif name == 'rotation_rounded_to_float32':
+        poses = poses.copy()
+        poses[:, :3, :3] = poses[:, :3, :3].astype(np.float32).astype(np.float64)
+    elif name in LIMIT or name == 'beyond_limit':
+        axis, sign = LIMIT.get(name, (0, 1))
+        bl = voxel * block
+        poses = poses.copy()
+        poses[:, axis, 3] += sign * (tsdf_ref.BLOCK_LIMIT * bl + (10.0 if name == 'beyond_limit' else -0.2))
+    elif name in INTRINSICS:
+        K = INTRINSICS[name]
+    elif name == 'one_row':
+        depth, K = depth[:, 30:31, :], (K[0], K[1], K[2], 0.0)
+    elif name == 'one_column':
+        depth, K = depth[:, :, 40:41], (K[0], K[1], 0.0, K[3])
+    elif name == 'one_pixel':
+        depth, K = depth[:, 30:31, 40:41], (K[0], K[1], 0.0, 0.0)
+    elif name == 'stride_beyond_image':
+        stride = 100
+    elif name == 'one_frame':
+        depth, poses = depth[:1], poses[:1]
+    else:
+        raise KeyError(name)
+    depth, poses = np.ascontiguousarray(depth), np.ascontiguousarray(poses)
+    depth.setflags(write=False)
+    poses.setflags(write=False)
+    return dict(depth=depth, K=tuple(float(v) for v in K), poses=poses, voxel=voxel, trunc=trunc, stride=stride)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_statement(name, block):
+    """the statement of `edge_case(name, block)`, with `updated` bool [nb,F]: the (block, frame) pairs it updates"""
+    c = edge_case(name, block)
+    out = tsdf_ref.tsdf_fragment(c['depth'], c['K'], c['poses'], c['voxel'], c['trunc'], block=block, stride=c['stride'],
+                                 return_updated=True)
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+def cull_keeps(case, blocks, block, row_norm=True):
+    """tsdf_ref.cull_keeps on a case dict (of `edge_case`, or made from a fixture) and the statement's block list"""
+    H, W = case['depth'].shape[1:]
+    return tsdf_ref.cull_keeps(blocks, case['K'], np.linalg.inv(case['poses']), H, W, case['voxel'], case['trunc'], 4.5, block,
+                               row_norm)

@@ -46,8 +46,10 @@ def _local(B):
     return np.stack([l % B, (l // B) % B, l // (B * B)], 1)    # l = (lz B + ly) B + lx
 
 
-def tsdf_integrate(blocks, depth, intrinsic, extrinsic, voxel_length, sdf_trunc, depth_scale, depth_trunc, block):
-    """(tsdf float32 [nb,B^3], weight int32 [nb,B^3]) after the frames 0..F-1 in order."""
+def tsdf_integrate(blocks, depth, intrinsic, extrinsic, voxel_length, sdf_trunc, depth_scale, depth_trunc, block,
+                   return_updated=False):
+    """(tsdf float32 [nb,B^3], weight int32 [nb,B^3]) after the frames 0..F-1 in order.  With `return_updated` also a bool
+    [nb,F]: frame f updates at least one voxel of the block (what a run on that frame alone leaves with weight > 0)."""
     fx, fy, cx, cy = (np.float64(v) for v in intrinsic)
     F, H, W = depth.shape
     B, nb = block, len(blocks)
@@ -57,6 +59,7 @@ def tsdf_integrate(blocks, depth, intrinsic, extrinsic, voxel_length, sdf_trunc,
     tsdf = np.zeros(len(pw), np.float32)
     weight = np.zeros(len(pw), np.int32)
     E = np.asarray(extrinsic, np.float64)
+    updated = np.zeros((nb, F), bool)
     for f in range(F):
         pcx, pcy, pcz = _rigid(E[f], x, y, z)
         sel = np.nonzero(pcz > 0)[0]
@@ -78,7 +81,33 @@ def tsdf_integrate(blocks, depth, intrinsic, extrinsic, voxel_length, sdf_trunc,
         w = weight[sel].astype(np.float64)
         tsdf[sel] = ((tsdf[sel].astype(np.float64) * w + val) / (w + 1.0)).astype(np.float32)
         weight[sel] += 1
+        updated[sel // B ** 3, f] = True
+    if return_updated:
+        return tsdf.reshape(nb, B ** 3), weight.reshape(nb, B ** 3), updated
     return tsdf.reshape(nb, B ** 3), weight.reshape(nb, B ** 3)
+
+
+def cull_keeps(blocks, intrinsic, extrinsic, height, width, voxel_length, sdf_trunc, depth_trunc, block, row_norm=True):
+    """bool [nb,F]: the per-frame block cull of `ts_integrate` (csrc/tsdf.hip) restated -- a frame is kept for a block unless
+    the ball of radius sqrt(3)/2 bl around the block's centre, stretched by max(1, the largest row norm of the extrinsic's
+    3x3 part), lies outside one of the six half-spaces an update needs.  `row_norm=False` leaves the stretch out: the rule
+    before it was made conservative for poses that are not rigid.  An instrument for the tests' premises (what would the
+    suite see if the rule were wrong?), NOT a second definition of the result: the cull never reaches the result."""
+    fx, fy, cx, cy = (np.float64(v) for v in intrinsic)
+    bl = np.float64(voxel_length) * np.float64(block)
+    c = (np.asarray(blocks, np.float64) + 0.5) * bl                              # [nb,3]
+    E = np.asarray(extrinsic, np.float64).reshape(-1, 4, 4)[:, :3]                # [F,3,4]
+    rad = 0.8660254037844387 * bl
+    margin = (rad * 1.01 + 1e-6 + 1e-9 * np.abs(c).sum(1))[:, None]              # [nb,1]
+    p = np.einsum('frk,bk->rbf', E[:, :, :3], c) + E[:, :, 3].T[:, None, :]      # [3,nb,F]
+    px, py, pz = p
+    stretch = np.maximum(1.0, np.sqrt((E[:, :, :3] ** 2).sum(2).max(1)))[None, :] if row_norm else 1.0
+    mg = margin * stretch + 1e-9 * np.abs(p).sum(0)
+    l, r, t, b = cx + 0.5, width - cx - 0.5, cy + 0.5, height - cy - 0.5
+    keep = (pz > -mg) & (pz - mg < depth_trunc + sdf_trunc) \
+        & (fx * px + l * pz >= -mg * (fx + abs(l))) & (fx * px - r * pz <= mg * (fx + abs(r))) \
+        & (fy * py + t * pz >= -mg * (fy + abs(t))) & (fy * py - b * pz <= mg * (fy + abs(b)))
+    return keep | ~(np.abs(p).sum(0) < 1e300)
 
 
 def tsdf_points(blocks, tsdf, weight, voxel_length, block, min_weight, return_cross=False):
@@ -129,16 +158,18 @@ def tsdf_points(blocks, tsdf, weight, voxel_length, block, min_weight, return_cr
 
 
 def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1000.0, depth_trunc=4.5, block=16, stride=4,
-                  min_weight=1, return_cross=False):
-    """dict(xyz, blocks, tsdf, weight[, cross]) of numpy arrays: the whole statement.  extrinsic = inv(pose) is taken on
+                  min_weight=1, return_cross=False, return_updated=False):
+    """dict(xyz, blocks, tsdf, weight[, cross][, updated]) of numpy arrays: the whole statement.  extrinsic = inv(pose) is taken on
     the host exactly as the wrapper takes it; the statement itself never inverts."""
     depth = np.ascontiguousarray(depth, np.uint16)
     pose = np.ascontiguousarray(pose, np.float64).reshape(-1, 4, 4)
     extrinsic = np.linalg.inv(pose)
     blocks = tsdf_blocks(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale, depth_trunc, block, stride)
-    tsdf, weight = tsdf_integrate(blocks, depth, intrinsic, extrinsic, voxel_length, sdf_trunc, depth_scale, depth_trunc,
-                                  block)
+    tsdf, weight, updated = tsdf_integrate(blocks, depth, intrinsic, extrinsic, voxel_length, sdf_trunc, depth_scale,
+                                           depth_trunc, block, return_updated=True)
     out = {'blocks': blocks, 'tsdf': tsdf, 'weight': weight}
+    if return_updated:
+        out['updated'] = updated
     if return_cross:
         out['xyz'], out['cross'] = tsdf_points(blocks, tsdf, weight, voxel_length, block, min_weight, True)
     else:
