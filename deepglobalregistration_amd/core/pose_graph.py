@@ -46,7 +46,8 @@ def rigid_inverse(T):
 
 def rotation_vectors(R):
     """`eval.metrics.rotation_vector` for a stack [m,3,3]: axis times angle, angle in [0, pi], with its care near 0 (the
-    antisymmetric part is the vector) and near pi (the axis from the symmetric part)."""
+    antisymmetric part is the vector) and near pi (the axis from the symmetric part, its sign from the antisymmetric
+    one)."""
     R = np.asarray(R, np.float64).reshape(-1, 3, 3)
     w = 0.5 * np.stack((R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]), 1)
     s = np.linalg.norm(w, axis=1)
@@ -59,6 +60,8 @@ def rotation_vectors(R):
         A = (R[k] + R[k].T) / 2.0 - c[k] * np.eye(3)
         j = int(np.argmax(np.diag(A)))
         a = A[j] / np.sqrt(max(A[j, j] * (1.0 - c[k]), 1e-300))
+        if float(a @ w[k]) < 0.0:      # the symmetric part knows the axis up to its sign: that is the antisymmetric part's
+            a = -a
         out[k] = a / np.linalg.norm(a) * angle[k]
     return out
 

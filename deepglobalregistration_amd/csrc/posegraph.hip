@@ -67,7 +67,10 @@ __device__ void pg_rotation_vector(const double *R, double *w) {
     return;
   }
   if (c > 0.0) return;
-  // angle -> pi: (R + R^T) / 2 - c I = (1 - c) a a^T; the row of the largest diagonal entry, normalised
+  // angle -> pi: (R + R^T) / 2 - c I = (1 - c) a a^T; the row of the largest diagonal entry, normalised.  That row knows
+  // the axis up to its sign; the sign is the antisymmetric part's (w = sin(angle) a: tiny here, but far above rounding),
+  // and where w is exactly zero the angle is pi and both signs are logarithms.  (2 w is taken from R again: w kept alive
+  // over A costs 4 registers more than the 256 at which two waves fit a SIMD.)
   double A[9];
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) A[3 * i + j] = 0.5 * (R[3 * i + j] + R[3 * j + i]) - (i == j ? c : 0.0);
@@ -76,7 +79,7 @@ __device__ void pg_rotation_vector(const double *R, double *w) {
   if (A[8] > A[4 * k]) k = 2;
   double a[3] = {A[3 * k], A[3 * k + 1], A[3 * k + 2]};
   const double nrm = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-  const double f = nrm > 0.0 ? angle / nrm : 0.0;
+  const double f = nrm > 0.0 ? copysign(angle / nrm, a[0] * (R[7] - R[5]) + a[1] * (R[2] - R[6]) + a[2] * (R[3] - R[1])) : 0.0;
   w[0] = a[0] * f; w[1] = a[1] * f; w[2] = a[2] * f;
 }
 

@@ -55,10 +55,14 @@ def rotation_vector(R):
         return w * (angle / s)
     if c > 0:                                   # angle -> 0: angle / sin(angle) -> 1
         return w
-    # angle -> pi: the axis from the symmetric part R + R^T = 2 cos I + 2 (1 - cos) a a^T, signed by its largest entry
+    # angle -> pi: the axis from the symmetric part R + R^T = 2 cos I + 2 (1 - cos) a a^T, which knows it up to its sign;
+    # the sign is the antisymmetric part's (w = sin(angle) a, tiny here but not noise: |w| >~ 1e-9 against 1e-16), and
+    # where w is exactly zero the angle is pi and both signs are logarithms
     A = (R + R.T) / 2.0 - c * np.eye(3)
     k = int(np.argmax(np.diag(A)))
     a = A[k] / np.sqrt(max(A[k, k] * (1.0 - c), 1e-300))
+    if float(a @ w) < 0.0:
+        a = -a
     return a / np.linalg.norm(a) * angle
 
 

@@ -2,7 +2,9 @@
 from C99 and refuses every bad argument before any device work; the Python wrappers refuse them before any device state
 exists; spanning tree, pruning, connectivity and the default mu on hand-made graphs; chi2 against
 `eval.metrics.information_rmse`; the analytic Jacobians of the reference solver against central differences; and the
-reference solver (tests/posegraph_ref.py: the yardstick of the GPU tests) against scipy's least squares on F*."""
+reference solver (tests/posegraph_ref.py: the yardstick of the GPU tests) against scipy's least squares on F*; the k-step
+comparison of the GPU tests -- its noise under a second float64 factorisation, the tolerances taken from it, the three
+mutants it must reject and the end-state criteria let through --; and the rotation logarithm next to pi for any axis."""
 import os
 import shutil
 import subprocess
@@ -349,3 +351,124 @@ def test_scene_mode_writes_the_optimised_trajectory(tmp_path):
     assert stats[1, :, 0].tolist() == [1, 1, 1, 0]               # pose graph: repaired; the unreachable fragment fails
     assert np.isinf(stats[1, 3, 1]) and rows == [('room', 4, 3, 4, 2, 2.0, 1.0, 3)]
     assert any('pose graph' in ln for ln in lines)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the k-step comparison (posegraph_ref.steps_check): its yardstick, its tolerances and what it can see
+_ALL = {**R.suite_graphs(), **R.step_graphs()}
+_STEP_REF = {name: {} for name in _ALL}                    # name -> {k: lm_solve(max_iter=k)}, shared by the tests below
+_SMALL = [name for name, g in _ALL.items() if g['n'] <= 20]
+
+
+def _lm(**kw):
+    return lambda g, k: R.lm_solve(*R.solve_args(g), max_iter=k, **kw)
+
+
+def test_step_graphs_are_what_they_are_for():
+    """The reject / re-damp loop really runs on the far starts, by the reference's own counter; the singular and
+    rank-deficient graphs are solved, finite; the counters are consistent."""
+    full = {name: R.lm_solve(*R.solve_args(g)) for name, g in R.step_graphs().items()}
+    for name, r in full.items():
+        print(f'{name}: {r["iterations"]} steps, {r["factorisations"]} factorisations, {r["rejections"]} rejected, '
+              f'converged {r["converged"]}, F* {r["objective_initial"]:.6g} -> {r["objective_final"]:.6g}')
+        assert r['converged'] and 1 <= r['iterations'] < 100 and np.isfinite(r['poses']).all()
+        assert r['factorisations'] == r['iterations'] + r['rejections']
+    assert full['far_n9']['rejections'] >= 4 and full['far_n13']['rejections'] >= 10
+    assert full['rank1_info']['rejections'] >= 4
+    g = R.step_graphs()['reference_last']
+    assert g['reference_node'] == g['n'] - 1
+    # max_iter = 0: nothing moves, nothing is factored
+    g = _ALL['n5']
+    r0 = R.lm_solve(*R.solve_args(g), max_iter=0)
+    assert r0['iterations'] == 0 and not r0['converged'] and r0['factorisations'] == 0
+    np.testing.assert_array_equal(r0['poses'], g['P_init'])
+    with pytest.raises(ValueError):
+        R.lm_solve(*R.solve_args(g), factor='lu')
+    with pytest.raises(ValueError):
+        R.lm_solve(*R.solve_args(g), mutant='none')
+
+
+def test_k_step_noise_of_two_factorisations_and_the_gpu_tolerances():
+    """The same k steps through two float64 factorisations of the same matrix (LAPACK's Cholesky; eigh + qr): their
+    largest pose-entry difference per class is the noise the GPU test's STEP_TOL is ten times of (with the floor of 64
+    ulp where the measured maximum is an ulp or two).  `steps_check` accepts the second factorisation on every graph at
+    those tolerances, and the constants recorded in tests/test_gpu_pose_graph.py still bound what is measured here."""
+    import test_gpu_pose_graph as G
+    noise, entry = {c: 0.0 for c in G.STEP_TOL}, {c: 0.0 for c in G.STEP_TOL}
+    for name, g in _ALL.items():
+        c = R.step_class(name, g)
+        rows = R.steps_check(_lm(factor='eigh_qr'), g, tol=G.STEP_TOL[c], reference=_STEP_REF[name])
+        worst = max(dp for _, _, _, dp in rows)
+        print(f'{name} [{c}]: |P_eigh_qr - P_cholesky| after k = {R.STEP_KS} steps: ' + ' '.join(f'{dp:.2e}' for _, _, _, dp in rows))
+        noise[c] = max(noise[c], worst)
+        entry[c] = max(entry[c], max(float(np.abs(ref['poses']).max()) for _, _, ref, _ in rows))
+    undecided = {(name, k) for name in _ALL for k, ref in _STEP_REF[name].items()
+                 if ref['decrease_ratio'] is not None and R.UNDECIDED[0] < ref['decrease_ratio'] < R.UNDECIDED[1]}
+    assert undecided == {('n3_triangle', 5)}, undecided       # the one stopping decision `steps_check` leaves to rounding
+    for c in G.STEP_TOL:
+        print(f'class {c}: measured noise {noise[c]:.3e} (recorded {G.STEP_NOISE[c]:.3e}), largest pose entry {entry[c]:.3f}, '
+              f'floor {G.STEP_FLOOR:.3e}, tolerance {G.STEP_TOL[c]:.3e}')
+        assert G.STEP_TOL[c] == 10 * max(G.STEP_NOISE[c], G.STEP_FLOOR)
+        assert 10 * noise[c] <= G.STEP_TOL[c]
+        if G.STEP_NOISE[c] < G.STEP_FLOOR:      # the floor decides: it was taken in the binade of the class's largest entry
+            assert 2.0 <= entry[c] < 4.0 and G.STEP_FLOOR == R.ulp64(entry[c])
+
+
+def _old_criteria(g, ref, got, pose_tol):
+    """The end-state criteria of test_gpu_pose_graph.test_reaches_the_reference_minimum, applied to a solver's result."""
+    F = pg.robust_objective(got['poses'], g['edges'], g['X'], g['info'], g['uncertain'], g['mu'])
+    line, out, unc = got['line_process'], g['outlier'], g['uncertain']
+    return bool(F <= ref['objective_final'] * (1 + 1e-9) + 1e-12 and F <= ref['objective_initial']
+                and (line[out] < 0.25).all() and (line[~out & unc] >= 0.25).all() and (line[~unc] == 1.0).all()
+                and np.abs(got['poses'] - ref['poses']).max() <= pose_tol and got['converged'] and 1 <= got['iterations'] <= 100)
+
+
+@pytest.mark.parametrize('mutant', R.MUTANTS)
+def test_steps_check_rejects_what_the_end_state_criteria_let_through(mutant):
+    """A solver with one deliberate error descends to the same minimum by another road: the end-state criteria pass it
+    (printed: on which graphs), `steps_check` does not -- on every graph with an uncertain edge; the graphs without one
+    cannot see 'weight_not_squared' (l = 1), and a single free node has no off-diagonal block to halve."""
+    import test_gpu_pose_graph as G
+    old, blind = [], []
+    for name in _SMALL:
+        g = _ALL[name]
+        full_ref = R.lm_solve(*R.solve_args(g))
+        full = R.lm_solve(*R.solve_args(g), mutant=mutant)
+        if _old_criteria(g, full_ref, full, G.POSE_TOL):
+            old.append(f'{name} ({full["iterations"]} steps, ref {full_ref["iterations"]})')
+        try:
+            R.steps_check(_lm(mutant=mutant), g, tol=G.STEP_TOL[R.step_class(name, g)], reference=_STEP_REF[name])
+        except AssertionError as e:
+            one = R.lm_solve(*R.solve_args(g), max_iter=1, mutant=mutant)
+            print(f'{mutant} / {name}: rejected ({e}); pose difference after one step '
+                  f'{np.abs(one["poses"] - _STEP_REF[name][1]["poses"]).max():.2e}')
+            continue
+        blind.append(name)
+        assert not g['uncertain'].any(), f'steps_check accepted the mutant {mutant} on {name}'
+    print(f'{mutant}: the end-state criteria pass it on {len(old)} of {len(_SMALL)} graphs: {old}')
+    print(f'{mutant}: steps_check cannot see it on {blind}')
+
+
+_PI_AXES = ((0.6, -0.48, 0.64), (0.6, -0.64, 0.48), (-0.8, 0.36, 0.48), (-0.6, -0.64, -0.48))
+_PI_GAPS = (1e-3, 2e-6, 1.5e-6, 5e-7, 1e-8, 0.0)
+
+
+@pytest.mark.parametrize('axis', _PI_AXES)
+def test_rotation_vector_next_to_pi_for_any_axis(axis):
+    """exp(log R) = R to 1e-10 for angle = pi - d on both sides of the switch to the symmetric part (sin(angle) = 1e-6;
+    the antisymmetric branch just above it is at 2.6e-11 already), whatever the sign of the axis' largest entry: the
+    symmetric part knows the axis up to its sign only.  At d = 0 both signs are logarithms."""
+    from deepglobalregistration_amd.eval.metrics import rotation_vector
+    a = np.array(axis) / np.linalg.norm(axis)
+    for d in _PI_GAPS:
+        Rm = R.so3_exp(a * (np.pi - d))
+        X = np.eye(4)
+        X[:3, :3], X[:3, 3] = Rm, (0.3, -0.2, 0.5)
+        E, xi = pg.edge_residuals(np.tile(np.eye(4), (2, 1, 1)), [[0, 1]], pg.rigid_inverse(X)[None])
+        for what, w in (('metrics.rotation_vector', rotation_vector(Rm)), ('pose_graph.rotation_vectors', pg.rotation_vectors(Rm[None])[0]),
+                        ('pose_graph.edge_residuals', xi[0, :3])):
+            err = np.abs(R.so3_exp(w) - Rm).max()
+            print(f'axis {axis} d={d:g} {what}: |exp(log R) - R| = {err:.2e}')
+            assert err <= 1e-10, (what, axis, d, err)
+            assert abs(np.linalg.norm(w) - (np.pi - d)) <= 1e-9
+        np.testing.assert_allclose(xi[0, 3:], X[:3, 3], rtol=0, atol=1e-15)
