@@ -112,6 +112,11 @@ SIGNATURES = {
                                     c_i64p, c_i64p, c_i64p, vp]),
     'dgr_tsdf_mesh': (C.c_int, [vp, vp, C.c_int64, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp, C.c_int64, vp, C.c_int64,
                                 c_i64p, c_i64p, vp]),
+    'dgr_tsdf_fragment_rgb': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, c_f64p, c_f64p, c_f64p, C.c_double, C.c_double,
+                                        C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64,
+                                        c_i64p, c_i64p, c_i64p, vp, vp, vp, vp]),
+    'dgr_tsdf_mesh_rgb': (C.c_int, [vp, vp, C.c_int64, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp, C.c_int64, vp, C.c_int64,
+                                    c_i64p, c_i64p, vp, vp, vp]),
     'dgr_debug_ortho2rotation': (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, vp]),
     'dgr_debug_se3_refine_from': (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_double,
                                             c_f64p, c_f64p, vp]),

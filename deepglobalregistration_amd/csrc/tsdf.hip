@@ -11,9 +11,10 @@
 //                  candidate of a key, flag = "I am that candidate", scan -> the block's place in the list
 //   ts_blocks      the flagged candidates write the block list                       -- host sync 1: nb
 //   ts_integrate   ONE WORKGROUP PER BLOCK (four per 16^3 block, a slab of z-layers each), voxel-stationary: a thread keeps
-//                  tsdf / weight of its voxels in registers over the whole frame loop and stores them once
+//                  tsdf / weight (with colour: and the three integer colour sums) of its voxels in registers over the whole
+//                  frame loop and stores them once
 //   ts_extract<0>  the same workgroups: crossings per workgroup; scan -> a workgroup's first point -- host sync 2: P
-//   ts_extract<1>  the same pass again, writing
+//   ts_extract<1>  the same pass again, writing (with colour: the point's colour beside its position)
 //
 // Determinism: a voxel is owned by one thread, frames are applied in order, output positions come from scans -- no
 // floating-point atomics, and the only integer atomics (hash insertion, a statistics counter) are order-free.
@@ -134,15 +135,26 @@ __global__ void __launch_bounds__(TS_THREADS)
 // lies outside one of these half-spaces by a margin of 1 % of the radius + 1e-6 + 1e-9 |centre|, orders of magnitude above
 // the rounding of either side; the bitwise comparison with the uncalled statement is the proof that nothing is lost.
 // workgroups per block: TsdfSplit (tsdf_common.h)
-template <int B>
+// COLOR (compile time; without it the kernel is the depth-only one, untouched by the rest): every update also adds the
+// pixel's colour, three byte loads from the caller's uint8 [F,H,W,3], to the voxel's three int32 sums, kept in registers
+// like tsdf / weight.  (Measured against one 32-bit load per update from words packed by a pre-pass: DESIGN.md 4.10.)  The
+// sums leave through LDS, so that a store instruction writes 256 consecutive words of the [voxel][3] layout.
+template <int B, bool COLOR>
 __global__ void __launch_bounds__(TS_THREADS)
     ts_integrate(const int32_t *__restrict__ bkeys, const uint16_t *__restrict__ depth, const double *__restrict__ dlut,
                  const double *__restrict__ mtab, const double *__restrict__ ext, TsCam cam, float *__restrict__ tsdf_out,
-                 int32_t *__restrict__ weight_out, unsigned long long *kept) {
+                 int32_t *__restrict__ weight_out, unsigned long long *kept, const uint8_t *__restrict__ color,
+                 int32_t *__restrict__ rgb_out) {
 #pragma clang fp contract(off)
   constexpr int SPLIT = TsdfSplit<B>::value, PART = B * B * B / SPLIT;
   constexpr int V = B * B * B, VPT = PART / TS_THREADS, ZSTEP = TS_THREADS / (B * B);
   __shared__ unsigned char keep[TS_THREADS];
+  __shared__ int32_t stage[COLOR ? VPT * TS_THREADS * 3 : 1];
+  int32_t rgb[COLOR ? VPT : 1][3];
+  if constexpr (COLOR) {
+#pragma unroll
+    for (int k = 0; k < VPT; ++k) rgb[k][0] = rgb[k][1] = rgb[k][2] = 0;
+  }
   const int b = blockIdx.x / SPLIT, part = blockIdx.x % SPLIT, t = threadIdx.x;
   const int bx = bkeys[(int64_t)b * 3], by = bkeys[(int64_t)b * 3 + 1], bz = bkeys[(int64_t)b * 3 + 2];
   const int lx = t % B, ly = (t / B) % B, lz0 = part * (B / SPLIT) + t / (B * B);
@@ -213,6 +225,11 @@ __global__ void __launch_bounds__(TS_THREADS)
         const double w = (double)weight[k];
         tsdf[k] = (float)(((double)tsdf[k] * w + val) / (w + 1.0));
         weight[k] += 1;
+        if constexpr (COLOR) {
+          const uint8_t *c = color + ((int64_t)f * cam.H * cam.W + (v * cam.W + u)) * 3;
+#pragma unroll
+          for (int e = 0; e < 3; ++e) rgb[k][e] += (int32_t)c[e];
+        }
       }
     }
   }
@@ -221,6 +238,17 @@ __global__ void __launch_bounds__(TS_THREADS)
     tsdf_out[(int64_t)b * V + part * PART + t + TS_THREADS * k] = tsdf[k];
     weight_out[(int64_t)b * V + part * PART + t + TS_THREADS * k] = weight[k];
   }
+  if constexpr (COLOR) {
+    // the slab's sums are PART * 3 consecutive words: voxel t + 256 k of the slab at stage[(t + 256 k) * 3 ..]
+#pragma unroll
+    for (int k = 0; k < VPT; ++k)
+#pragma unroll
+      for (int e = 0; e < 3; ++e) stage[(t + TS_THREADS * k) * 3 + e] = rgb[k][e];
+    __syncthreads();
+    int32_t *out = rgb_out + ((int64_t)b * V + part * PART) * 3;
+#pragma unroll
+    for (int j = 0; j < VPT * 3; ++j) out[t + TS_THREADS * j] = stage[t + TS_THREADS * j];
+  }
   if (kept && nkept && part == 0) atomicAdd(kept, (unsigned long long)nkept);
 }
 
@@ -228,13 +256,14 @@ __global__ void __launch_bounds__(TS_THREADS)
 // block-major keeps the output order).  Thread t owns the voxels [t VPT, (t + 1) VPT) of the slab in ascending l -- 8 or 16
 // contiguous bytes per lane and array, a coalesced load -- so a workgroup-wide exclusive scan of the threads' counts is a
 // voxel's place in the workgroup's output.  WRITE = 0: counts[workgroup] only.  WRITE = 1: the same tests again and the
-// points, from base[workgroup] on.  The +x / +y / +z neighbour blocks are looked up once per workgroup.
-template <int B, int WRITE>
+// points, from base[workgroup] on.  The +x / +y / +z neighbour blocks are looked up once per workgroup.  COLOR (compile
+// time, with WRITE = 1; without it the kernel is the depth-only one): the point's colour too, from the ends' colour sums.
+template <int B, int WRITE, bool COLOR = false>
 __global__ void __launch_bounds__(TS_THREADS)
     ts_extract(const int32_t *__restrict__ bkeys, const float *__restrict__ tsdf, const int32_t *__restrict__ weight,
                const int32_t *__restrict__ table, uint32_t mask, const int32_t *__restrict__ keys, const int32_t *__restrict__ rank,
                double voxel, int min_weight, int32_t *__restrict__ counts, const int32_t *__restrict__ base, int64_t max_points,
-               double *__restrict__ xyz) {
+               double *__restrict__ xyz, const int32_t *__restrict__ rgb, double *__restrict__ pcolor) {
 #pragma clang fp contract(off)
   constexpr int SPLIT = TsdfSplit<B>::value, PART = B * B * B / SPLIT;
   constexpr int V = B * B * B, VPT = PART / TS_THREADS;
@@ -294,9 +323,17 @@ __global__ void __launch_bounds__(TS_THREADS)
       if (!crossing(l, lc, a, f0, f1)) continue;
       if (at < max_points) {   // (always: the host checked P <= max_points before this launch)
         double p[3];
-        tsdf_crossing_point<B>(bc, lc, a, f0, f1, voxel, p);
+        const double r = tsdf_crossing_point<B>(bc, lc, a, f0, f1, voxel, p);
 #pragma unroll
         for (int e = 0; e < 3; ++e) xyz[at * 3 + e] = p[e];
+        if constexpr (COLOR) {   // the two ends once more: the voxel and the neighbour `crossing` read
+          const int64_t o0 = (int64_t)b * V + l;
+          const int64_t o1 = lc[a] + 1 < B ? o0 + STR[a] : (int64_t)nbr[a] * V + (l - (B - 1) * STR[a]);
+          double c[3];
+          tsdf_crossing_color(rgb + o0 * 3, weight[o0], rgb + o1 * 3, weight[o1], r, c);
+#pragma unroll
+          for (int e = 0; e < 3; ++e) pcolor[at * 3 + e] = c[e];
+        }
       }
       ++at;
     }
@@ -307,26 +344,38 @@ template <int B>
 static int ts_run_blocks(const int32_t *bkeys, int64_t nb, const uint16_t *depth, const double *dlut, const double *mtab,
                          const double *ext, const TsCam &cam, float *tsdf, int32_t *weight, unsigned long long *kept,
                          const int32_t *table, uint32_t mask, const int32_t *keys, const int32_t *rank, int min_weight,
-                         int32_t *counts, hipStream_t stream) {
-  ts_integrate<B><<<(unsigned)(nb * TsdfSplit<B>::value), TS_THREADS, 0, stream>>>(bkeys, depth, dlut, mtab, ext, cam, tsdf, weight, kept);
-  ts_extract<B, 0><<<(unsigned)(nb * TsdfSplit<B>::value), TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight,
-                                                            counts, nullptr, 0, nullptr);
+                         int32_t *counts, const uint8_t *color, int32_t *rgb, hipStream_t stream) {
+  const unsigned grid = (unsigned)(nb * TsdfSplit<B>::value);
+  if (color)
+    ts_integrate<B, true><<<grid, TS_THREADS, 0, stream>>>(bkeys, depth, dlut, mtab, ext, cam, tsdf, weight, kept, color, rgb);
+  else
+    ts_integrate<B, false><<<grid, TS_THREADS, 0, stream>>>(bkeys, depth, dlut, mtab, ext, cam, tsdf, weight, kept, nullptr, nullptr);
+  ts_extract<B, 0><<<grid, TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight, counts,
+                                                    nullptr, 0, nullptr, nullptr, nullptr);
   DGR_LAUNCH_CHECK();
   return DGR_OK;
 }
 
-extern "C" int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframes, int height, int width,
-                                 const double *intrinsic, const double *pose, const double *extrinsic, double voxel_length,
-                                 double sdf_trunc, double depth_scale, double depth_trunc, int block, int stride,
-                                 int min_weight, double *xyz_out, int64_t max_points, int32_t *blocks_out, float *tsdf_out,
-                                 int32_t *weight_out, int64_t max_blocks, int64_t *n_blocks_out, int64_t *n_points_out,
-                                 int64_t *kept_out, dgr_stream stream_) {
+// The one body of dgr_tsdf_fragment (has_color = false: color, rgb_sum_out and point_color_out are not looked at) and
+// dgr_tsdf_fragment_rgb.
+static int ts_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframes, int height, int width, const double *intrinsic,
+                       const double *pose, const double *extrinsic, double voxel_length, double sdf_trunc, double depth_scale,
+                       double depth_trunc, int block, int stride, int min_weight, double *xyz_out, int64_t max_points,
+                       int32_t *blocks_out, float *tsdf_out, int32_t *weight_out, int64_t max_blocks, int64_t *n_blocks_out,
+                       int64_t *n_points_out, int64_t *kept_out, bool has_color, const uint8_t *color, int32_t *rgb_sum_out,
+                       double *point_color_out, dgr_stream stream_) {
   // argument errors first: nothing has touched the device when one of them is reported
   DGR_REQUIRE(ctx && depth && intrinsic && pose && extrinsic && n_blocks_out && n_points_out, "dgr_tsdf_fragment: NULL argument");
   DGR_REQUIRE(xyz_out || max_points == 0, "dgr_tsdf_fragment: xyz_out is NULL but max_points = %lld", (long long)max_points);
-  const bool want_volume = blocks_out || tsdf_out || weight_out;
+  const bool want_volume = blocks_out || tsdf_out || weight_out || (has_color && rgb_sum_out);
   DGR_REQUIRE(!want_volume || (blocks_out && tsdf_out && weight_out),
               "dgr_tsdf_fragment: blocks_out, tsdf_out and weight_out go together");
+  if (has_color) {
+    DGR_REQUIRE(color, "dgr_tsdf_fragment_rgb: color is NULL");
+    DGR_REQUIRE(!want_volume || rgb_sum_out, "dgr_tsdf_fragment_rgb: rgb_sum_out goes together with blocks_out, tsdf_out and weight_out");
+    DGR_REQUIRE(nframes <= DGR_TSDF_COLOR_MAX_FRAMES, "dgr_tsdf_fragment_rgb: %d frames: more than %d, a voxel's colour sum could pass 2^31",
+                nframes, DGR_TSDF_COLOR_MAX_FRAMES);
+  }
   DGR_REQUIRE(max_points >= 0 && max_blocks >= 0, "dgr_tsdf_fragment: negative capacity");
   DGR_REQUIRE(nframes >= 1 && height >= 1 && width >= 1, "dgr_tsdf_fragment: depth must be [F,H,W] with F, H, W >= 1, got [%d,%d,%d]",
               nframes, height, width);
@@ -403,12 +452,13 @@ extern "C" int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframe
     dgr_set_error("dgr_tsdf_fragment: %lld blocks of %d^3 voxels: 2^31 or more edges", (long long)nb, block);
     return DGR_ENOMEM;
   }
-  int32_t *bkeys = blocks_out, *weight = weight_out, *counts, *base;
+  int32_t *bkeys = blocks_out, *weight = weight_out, *rgb = has_color ? rgb_sum_out : nullptr, *counts, *base;
   float *tsdf = tsdf_out;
   if (!want_volume) {
     DGR_ALLOC(bkeys, A, int32_t, nb * 3);
     DGR_ALLOC(tsdf, A, float, nb * V);
     DGR_ALLOC(weight, A, int32_t, nb * V);
+    if (has_color) DGR_ALLOC(rgb, A, int32_t, nb * V * 3);
   }
   const int64_t ngroups = nb * (block == 16 ? TsdfSplit<16>::value : TsdfSplit<8>::value);   // workgroups of the per-block kernels
   DGR_ALLOC(counts, A, int32_t, ngroups);
@@ -417,10 +467,10 @@ extern "C" int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframe
   unsigned long long *kept = kept_out ? reinterpret_cast<unsigned long long *>(counters + 2) : nullptr;
   if (block == 8)
     DGR_CHECK(ts_run_blocks<8>(bkeys, nb, depth, dlut, mtab, ext_dev, cam, tsdf, weight, kept, table, mask, keys, rank,
-                               min_weight, counts, stream));
+                               min_weight, counts, has_color ? color : nullptr, rgb, stream));
   else
     DGR_CHECK(ts_run_blocks<16>(bkeys, nb, depth, dlut, mtab, ext_dev, cam, tsdf, weight, kept, table, mask, keys, rank,
-                                min_weight, counts, stream));
+                                min_weight, counts, has_color ? color : nullptr, rgb, stream));
   DGR_CHECK(dgr_exclusive_scan_i32(A, counts, base, ngroups, counters + 1, stream));
   DGR_HIP_CHECK(hipMemcpyAsync(pin, counters, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   DGR_CHECK(dgr_ctx_wait(ctx, stream));   // synchronisation 2: the number of points
@@ -438,12 +488,36 @@ extern "C" int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframe
     return DGR_ENOMEM;
   }
   if (P == 0) return DGR_OK;
-  if (block == 8)
-    ts_extract<8, 1><<<(unsigned)(nb * TsdfSplit<8>::value), TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight,
-                                                              nullptr, base, max_points, xyz_out);
-  else
-    ts_extract<16, 1><<<(unsigned)(nb * TsdfSplit<16>::value), TS_THREADS, 0, stream>>>(bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight,
-                                                               nullptr, base, max_points, xyz_out);
+  double *pcolor = has_color ? point_color_out : nullptr;
+#define TS_EXTRACT_ARGS bkeys, tsdf, weight, table, mask, keys, rank, cam.voxel, min_weight, nullptr, base, max_points, xyz_out, rgb, pcolor
+  if (block == 8 && !pcolor) ts_extract<8, 1, false><<<(unsigned)(nb * TsdfSplit<8>::value), TS_THREADS, 0, stream>>>(TS_EXTRACT_ARGS);
+  if (block == 8 && pcolor) ts_extract<8, 1, true><<<(unsigned)(nb * TsdfSplit<8>::value), TS_THREADS, 0, stream>>>(TS_EXTRACT_ARGS);
+  if (block == 16 && !pcolor) ts_extract<16, 1, false><<<(unsigned)(nb * TsdfSplit<16>::value), TS_THREADS, 0, stream>>>(TS_EXTRACT_ARGS);
+  if (block == 16 && pcolor) ts_extract<16, 1, true><<<(unsigned)(nb * TsdfSplit<16>::value), TS_THREADS, 0, stream>>>(TS_EXTRACT_ARGS);
+#undef TS_EXTRACT_ARGS
   DGR_LAUNCH_CHECK();
   return DGR_OK;
+}
+
+extern "C" int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframes, int height, int width,
+                                 const double *intrinsic, const double *pose, const double *extrinsic, double voxel_length,
+                                 double sdf_trunc, double depth_scale, double depth_trunc, int block, int stride,
+                                 int min_weight, double *xyz_out, int64_t max_points, int32_t *blocks_out, float *tsdf_out,
+                                 int32_t *weight_out, int64_t max_blocks, int64_t *n_blocks_out, int64_t *n_points_out,
+                                 int64_t *kept_out, dgr_stream stream) {
+  return ts_fragment(ctx, depth, nframes, height, width, intrinsic, pose, extrinsic, voxel_length, sdf_trunc, depth_scale,
+                     depth_trunc, block, stride, min_weight, xyz_out, max_points, blocks_out, tsdf_out, weight_out, max_blocks,
+                     n_blocks_out, n_points_out, kept_out, false, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int dgr_tsdf_fragment_rgb(dgr_ctx *ctx, const uint16_t *depth, int nframes, int height, int width,
+                                     const double *intrinsic, const double *pose, const double *extrinsic,
+                                     double voxel_length, double sdf_trunc, double depth_scale, double depth_trunc, int block,
+                                     int stride, int min_weight, double *xyz_out, int64_t max_points, int32_t *blocks_out,
+                                     float *tsdf_out, int32_t *weight_out, int64_t max_blocks, int64_t *n_blocks_out,
+                                     int64_t *n_points_out, int64_t *kept_out, const uint8_t *color, int32_t *rgb_sum_out,
+                                     double *point_color_out, dgr_stream stream) {
+  return ts_fragment(ctx, depth, nframes, height, width, intrinsic, pose, extrinsic, voxel_length, sdf_trunc, depth_scale,
+                     depth_trunc, block, stride, min_weight, xyz_out, max_points, blocks_out, tsdf_out, weight_out, max_blocks,
+                     n_blocks_out, n_points_out, kept_out, true, color, rgb_sum_out, point_color_out, stream);
 }

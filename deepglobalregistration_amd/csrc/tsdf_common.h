@@ -27,3 +27,16 @@ __device__ __forceinline__ double tsdf_crossing_point(const int32_t bc[3], const
   p[a] = p[a] + voxel * r;
   return r;
 }
+
+// c = the colour of that crossing in [0, 1]: the two ends' mean colours (rgb_sum / weight, exact integer sums over the
+// frames that updated the voxel) blended with the very r that places the point.  s0 / s1 point at the three sums of the
+// voxel and of its +a neighbour; w0, w1 >= min_weight >= 1.  DEFINED without fma, like the position.
+__device__ __forceinline__ void tsdf_crossing_color(const int32_t *__restrict__ s0, int32_t w0, const int32_t *__restrict__ s1,
+                                                    int32_t w1, double r, double c[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    const double m0 = (double)s0[e] / (double)w0, m1 = (double)s1[e] / (double)w1;
+    c[e] = (m0 + r * (m1 - m0)) / 255.0;
+  }
+}

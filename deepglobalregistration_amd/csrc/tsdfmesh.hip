@@ -11,7 +11,8 @@
 //                 workgroup's are looked up once, the slab's (B+1)^2 x (layers+1) corner states (negative / positive /
 //                 unusable) are staged in LDS, and both counts -- crossings and triangles -- come from the states alone
 //   scans         a workgroup's first vertex and first triangle                      -- the call's ONE host sync: P, T, flag
-//   ms_pass<1>    the same tests again: positions, normals, and every edge's vertex index (-1: none) into edge_vertex
+//   ms_pass<1>    the same tests again: positions, normals, with colour sums the vertex colours (tsdf_common.h's formula:
+//                 the fragment's point colours), and every edge's vertex index (-1: none) into edge_vertex
 //   ms_pass<2>    the configurations again: the table's triangles, their corners read from edge_vertex
 //
 // Determinism: a voxel, its three edges and its cell belong to one thread, output positions come from scans, and the only
@@ -69,14 +70,15 @@ struct MsView {
 };
 
 // MODE 0: vcounts / tcounts[workgroup].  MODE 1: vertices from vbase[workgroup] on.  MODE 2: triangles from tbase[workgroup] on.
-// Thread t owns the voxels (= cells) [t VPT, (t + 1) VPT) of the slab in ascending l, as in ts_extract.
-template <int B, int MODE>
+// Thread t owns the voxels (= cells) [t VPT, (t + 1) VPT) of the slab in ascending l, as in ts_extract.  COLOR (compile time,
+// with MODE 1; without it the kernel is the one without colour): the vertex's colour too, from the ends' colour sums.
+template <int B, int MODE, bool COLOR = false>
 __global__ void __launch_bounds__(MS_THREADS)
     ms_pass(const int32_t *__restrict__ blocks, const float *__restrict__ tsdf, const int32_t *__restrict__ weight,
             const int32_t *__restrict__ table, uint32_t mask, double voxel, int min_weight, int32_t *__restrict__ vcounts,
             int32_t *__restrict__ tcounts, const int32_t *__restrict__ vbase, const int32_t *__restrict__ tbase,
             int32_t *__restrict__ edge_vertex, int64_t max_vertices, int64_t max_triangles, double *__restrict__ xyz,
-            double *__restrict__ normal, int32_t *__restrict__ tri) {
+            double *__restrict__ normal, int32_t *__restrict__ tri, const int32_t *__restrict__ rgb, double *__restrict__ color) {
 #pragma clang fp contract(off)
   constexpr int SPLIT = TsdfSplit<B>::value, V = B * B * B, PART = V / SPLIT, VPT = PART / MS_THREADS;
   constexpr int LAYERS = B / SPLIT, TX = B + 1, TZ = LAYERS + 1, TILE = TX * TX * TZ;
@@ -152,11 +154,18 @@ __global__ void __launch_bounds__(MS_THREADS)
         if (at < max_vertices) {   // (always: the host checked P <= max_vertices before this launch)
           int hc[3] = {lc[0], lc[1], lc[2]};
           hc[a] += 1;
-          const float f0 = tsdf[(int64_t)b * V + l], f1 = tsdf[view.at(hc[0], hc[1], hc[2])];
+          const int64_t o0 = (int64_t)b * V + l, o1 = view.at(hc[0], hc[1], hc[2]);
+          const float f0 = tsdf[o0], f1 = tsdf[o1];
           double p[3];
           const double r = tsdf_crossing_point<B>(bc, lc, a, f0, f1, voxel, p);
 #pragma unroll
           for (int e = 0; e < 3; ++e) xyz[at * 3 + e] = p[e];
+          if constexpr (COLOR) {
+            double c[3];
+            tsdf_crossing_color(rgb + o0 * 3, weight[o0], rgb + o1 * 3, weight[o1], r, c);
+#pragma unroll
+            for (int e = 0; e < 3; ++e) color[at * 3 + e] = c[e];
+          }
           if (normal) {
             double n[3];
 #pragma unroll
@@ -205,24 +214,32 @@ template <int B>
 static void ms_launch(int mode, int64_t nb, const int32_t *blocks, const float *tsdf, const int32_t *weight, const int32_t *table,
                       uint32_t mask, double voxel, int min_weight, int32_t *vcounts, int32_t *tcounts, const int32_t *vbase,
                       const int32_t *tbase, int32_t *edge_vertex, int64_t max_vertices, int64_t max_triangles, double *xyz,
-                      double *normal, int32_t *tri, hipStream_t stream) {
+                      double *normal, int32_t *tri, const int32_t *rgb, double *color, hipStream_t stream) {
   const unsigned grid = (unsigned)(nb * TsdfSplit<B>::value);
 #define MS_ARGS blocks, tsdf, weight, table, mask, voxel, min_weight, vcounts, tcounts, vbase, tbase, edge_vertex, max_vertices, \
-                max_triangles, xyz, normal, tri
+                max_triangles, xyz, normal, tri, rgb, color
   if (mode == 0) ms_pass<B, 0><<<grid, MS_THREADS, 0, stream>>>(MS_ARGS);
-  if (mode == 1) ms_pass<B, 1><<<grid, MS_THREADS, 0, stream>>>(MS_ARGS);
+  if (mode == 1 && !color) ms_pass<B, 1, false><<<grid, MS_THREADS, 0, stream>>>(MS_ARGS);
+  if (mode == 1 && color) ms_pass<B, 1, true><<<grid, MS_THREADS, 0, stream>>>(MS_ARGS);
   if (mode == 2) ms_pass<B, 2><<<grid, MS_THREADS, 0, stream>>>(MS_ARGS);
 #undef MS_ARGS
 }
 
-extern "C" int dgr_tsdf_mesh(dgr_ctx *ctx, const int32_t *blocks, int64_t n_blocks, const float *tsdf, const int32_t *weight,
-                             int block, double voxel_length, int min_weight, double *xyz_out, double *normal_out,
-                             int64_t max_vertices, int32_t *tri_out, int64_t max_triangles, int64_t *n_vertices_out,
-                             int64_t *n_triangles_out, dgr_stream stream_) {
+// The one body of dgr_tsdf_mesh (has_color = false: rgb_sum and color_out are not looked at) and dgr_tsdf_mesh_rgb.
+static int ms_mesh(dgr_ctx *ctx, const int32_t *blocks, int64_t n_blocks, const float *tsdf, const int32_t *weight, int block,
+                   double voxel_length, int min_weight, double *xyz_out, double *normal_out, int64_t max_vertices,
+                   int32_t *tri_out, int64_t max_triangles, int64_t *n_vertices_out, int64_t *n_triangles_out, bool has_color,
+                   const int32_t *rgb_sum, double *color_out, dgr_stream stream_) {
   // argument errors first: nothing has touched the device when one of them is reported
   DGR_REQUIRE(ctx && n_vertices_out && n_triangles_out, "dgr_tsdf_mesh: NULL argument");
   DGR_REQUIRE(n_blocks >= 0, "dgr_tsdf_mesh: n_blocks = %lld", (long long)n_blocks);
   DGR_REQUIRE(n_blocks == 0 || (blocks && tsdf && weight), "dgr_tsdf_mesh: NULL argument");
+  if (has_color) {
+    DGR_REQUIRE(n_blocks == 0 || rgb_sum, "dgr_tsdf_mesh_rgb: rgb_sum is NULL");
+    DGR_REQUIRE(color_out || max_vertices == 0, "dgr_tsdf_mesh_rgb: color_out is NULL but max_vertices = %lld", (long long)max_vertices);
+  } else {
+    rgb_sum = nullptr, color_out = nullptr;
+  }
   DGR_REQUIRE(max_vertices >= 0 && max_triangles >= 0, "dgr_tsdf_mesh: negative capacity");
   DGR_REQUIRE(xyz_out || max_vertices == 0, "dgr_tsdf_mesh: xyz_out is NULL but max_vertices = %lld", (long long)max_vertices);
   DGR_REQUIRE(tri_out || max_triangles == 0, "dgr_tsdf_mesh: tri_out is NULL but max_triangles = %lld", (long long)max_triangles);
@@ -257,10 +274,10 @@ extern "C" int dgr_tsdf_mesh(dgr_ctx *ctx, const int32_t *blocks, int64_t n_bloc
   auto launch = [&](int mode) {
     if (block == 8)
       ms_launch<8>(mode, nb, blocks, tsdf, weight, table, mask, voxel_length, min_weight, vcounts, tcounts, vbase, tbase,
-                   edge_vertex, max_vertices, max_triangles, xyz_out, normal_out, tri_out, stream);
+                   edge_vertex, max_vertices, max_triangles, xyz_out, normal_out, tri_out, rgb_sum, color_out, stream);
     else
       ms_launch<16>(mode, nb, blocks, tsdf, weight, table, mask, voxel_length, min_weight, vcounts, tcounts, vbase, tbase,
-                    edge_vertex, max_vertices, max_triangles, xyz_out, normal_out, tri_out, stream);
+                    edge_vertex, max_vertices, max_triangles, xyz_out, normal_out, tri_out, rgb_sum, color_out, stream);
   };
   launch(0);
   DGR_LAUNCH_CHECK();
@@ -291,4 +308,20 @@ extern "C" int dgr_tsdf_mesh(dgr_ctx *ctx, const int32_t *blocks, int64_t n_bloc
   if (T > 0) launch(2);
   DGR_LAUNCH_CHECK();
   return DGR_OK;
+}
+
+extern "C" int dgr_tsdf_mesh(dgr_ctx *ctx, const int32_t *blocks, int64_t n_blocks, const float *tsdf, const int32_t *weight,
+                             int block, double voxel_length, int min_weight, double *xyz_out, double *normal_out,
+                             int64_t max_vertices, int32_t *tri_out, int64_t max_triangles, int64_t *n_vertices_out,
+                             int64_t *n_triangles_out, dgr_stream stream) {
+  return ms_mesh(ctx, blocks, n_blocks, tsdf, weight, block, voxel_length, min_weight, xyz_out, normal_out, max_vertices, tri_out,
+                 max_triangles, n_vertices_out, n_triangles_out, false, nullptr, nullptr, stream);
+}
+
+extern "C" int dgr_tsdf_mesh_rgb(dgr_ctx *ctx, const int32_t *blocks, int64_t n_blocks, const float *tsdf, const int32_t *weight,
+                                 int block, double voxel_length, int min_weight, double *xyz_out, double *normal_out,
+                                 int64_t max_vertices, int32_t *tri_out, int64_t max_triangles, int64_t *n_vertices_out,
+                                 int64_t *n_triangles_out, const int32_t *rgb_sum, double *color_out, dgr_stream stream) {
+  return ms_mesh(ctx, blocks, n_blocks, tsdf, weight, block, voxel_length, min_weight, xyz_out, normal_out, max_vertices, tri_out,
+                 max_triangles, n_vertices_out, n_triangles_out, true, rgb_sum, color_out, stream);
 }

@@ -52,10 +52,11 @@ _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short':
               'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
 
 
-def read_ply(filename):
+def read_ply(filename, *, return_colors=False):
     """Vertex positions [N,3] float64 of an ASCII or binary PLY (what `np.asarray(o3d.io.read_point_cloud(f)
     .points)` returns).  Other vertex properties and other elements are skipped; list properties are only
-    supported on elements after `vertex` (e.g. faces), which are not read."""
+    supported on elements after `vertex` (e.g. faces), which are not read.  With `return_colors` the pair (positions,
+    colours uint8 [N,3] of the properties red, green, blue, or None when the file has none)."""
     with open(filename, 'rb') as f:
         if f.readline().strip() != b'ply':
             raise ValueError(f'{filename}: not a PLY file')
@@ -88,28 +89,62 @@ def read_ply(filename):
         if fmt == 'ascii':
             rows = [f.readline().split() for _ in range(n)]
             data = np.array(rows, dtype=np.float64).reshape(n, len(names)) if n else np.zeros((0, len(names)))
-            return np.stack([data[:, names.index(k)] for k in 'xyz'], 1)
-        order = '<' if fmt == 'binary_little_endian' else '>'
-        dt = np.dtype([(p[1], order + _PLY_TYPES[p[0]]) for p in props])
-        data = np.frombuffer(f.read(dt.itemsize * n), dtype=dt, count=n)
-        return np.stack([data[k].astype(np.float64) for k in 'xyz'], 1)
+            col = {k: data[:, i] for i, k in enumerate(names)}
+        else:
+            order = '<' if fmt == 'binary_little_endian' else '>'
+            dt = np.dtype([(p[1], order + _PLY_TYPES[p[0]]) for p in props])
+            data = np.frombuffer(f.read(dt.itemsize * n), dtype=dt, count=n)
+            col = {k: data[k] for k in names}
+        xyz = np.stack([col[k].astype(np.float64) for k in 'xyz'], 1)
+        return (xyz, _ply_colors(col)) if return_colors else xyz
 
 
-def write_ply(filename, xyz, binary=True):
-    xyz = np.asarray(xyz, np.float64)
+_PLY_RGB = ('red', 'green', 'blue')
+
+
+def _ply_colors(col):
+    """uint8 [N,3] of a vertex element's columns red, green, blue; None without them"""
+    if not all(k in col for k in _PLY_RGB):
+        return None
+    return np.stack([np.asarray(col[k]).astype(np.uint8) for k in _PLY_RGB], 1)
+
+
+def _ply_vertex_block(cols, colors, binary):
+    """(header lines, bytes) of a vertex element: the float64 columns `cols` ([N,k] with their k names) as `property
+    double`, then -- with `colors` float [N,3] in [0, 1] -- `property uchar` red, green, blue (Open3D's order: positions,
+    normals, colours), the byte clip(rint(255 c), 0, 255)."""
+    rows, names = cols
+    header = ''.join(f'property double {k}\n' for k in names)
+    if colors is None:
+        if binary:
+            return header, rows.astype('<f8').tobytes()
+        return header, b''.join((' '.join(f'{v:.17g}' for v in r) + '\n').encode() for r in rows)
+    colors = np.asarray(colors, np.float64).reshape(-1, 3)
+    if len(colors) != len(rows):
+        raise ValueError(f'colors {colors.shape} do not match the {len(rows)} vertices')
+    rgb = np.clip(np.rint(255.0 * colors), 0, 255).astype(np.uint8)
+    header += ''.join(f'property uchar {k}\n' for k in _PLY_RGB)
+    if binary:
+        rec = np.empty(len(rows), np.dtype([('v', '<f8', len(names)), ('c', 'u1', 3)]))
+        rec['v'], rec['c'] = rows, rgb
+        return header, rec.tobytes()
+    return header, b''.join((' '.join(f'{v:.17g}' for v in r) + f' {c[0]} {c[1]} {c[2]}\n').encode() for r, c in zip(rows, rgb))
+
+
+def write_ply(filename, xyz, binary=True, colors=None):
+    """Points as PLY: double x y z, with `colors` (float [N,3] in [0, 1]) then uchar red green blue."""
+    xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
+    props, body = _ply_vertex_block((xyz, ['x', 'y', 'z']), colors, binary)
     with open(filename, 'wb') as f:
         f.write(b'ply\nformat ' + (b'binary_little_endian' if binary else b'ascii') + b' 1.0\n')
-        f.write(f'element vertex {len(xyz)}\nproperty double x\nproperty double y\nproperty double z\nend_header\n'.encode())
-        if binary:
-            f.write(xyz.astype('<f8').tobytes())
-        else:
-            for p in xyz:
-                f.write(f'{p[0]:.17g} {p[1]:.17g} {p[2]:.17g}\n'.encode())
+        f.write(f'element vertex {len(xyz)}\n{props}end_header\n'.encode())
+        f.write(body)
 
 
-def write_ply_mesh(filename, xyz, triangles, normals=None, binary=True):
-    """A triangle mesh as PLY: vertices double x y z (then double nx ny nz with `normals`), faces as `property list uchar
-    int vertex_indices`.  The vertex block is what `write_ply` writes, so `read_ply` returns the same points."""
+def write_ply_mesh(filename, xyz, triangles, normals=None, binary=True, colors=None):
+    """A triangle mesh as PLY: vertices double x y z (then double nx ny nz with `normals`, then uchar red green blue with
+    `colors`, float [N,3] in [0, 1]), faces as `property list uchar int vertex_indices`.  The vertex block is what
+    `write_ply` writes, so `read_ply` returns the same points."""
     xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
     tri = np.asarray(triangles).reshape(-1, 3)
     if tri.dtype.kind not in 'iu':
@@ -124,25 +159,24 @@ def write_ply_mesh(filename, xyz, triangles, normals=None, binary=True):
         cols.append(normals)
     rows = np.concatenate(cols, 1)
     names = ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if normals is not None else [])
+    props, body = _ply_vertex_block((rows, names), colors, binary)
     with open(filename, 'wb') as f:
         f.write(b'ply\nformat ' + (b'binary_little_endian' if binary else b'ascii') + b' 1.0\n')
-        f.write(f'element vertex {len(xyz)}\n'.encode() + ''.join(f'property double {k}\n' for k in names).encode())
+        f.write(f'element vertex {len(xyz)}\n{props}'.encode())
         f.write(f'element face {len(tri)}\nproperty list uchar int vertex_indices\nend_header\n'.encode())
+        f.write(body)
         if binary:
-            f.write(rows.astype('<f8').tobytes())
             faces = np.empty(len(tri), np.dtype([('n', 'u1'), ('v', '<i4', 3)]))
             faces['n'], faces['v'] = 3, tri
             f.write(faces.tobytes())
         else:
-            for r in rows:
-                f.write((' '.join(f'{v:.17g}' for v in r) + '\n').encode())
             for t in tri:
                 f.write(f'3 {t[0]} {t[1]} {t[2]}\n'.encode())
 
 
 def read_ply_mesh(filename):
-    """dict(xyz float64 [N,3], triangles int32 [T,3][, normals float64 [N,3]]) of an ASCII or binary PLY whose elements
-    are `vertex` (scalar properties) and then `face` (one list property of three indices per face)."""
+    """dict(xyz float64 [N,3], triangles int32 [T,3][, normals float64 [N,3]][, colors uint8 [N,3]]) of an ASCII or binary
+    PLY whose elements are `vertex` (scalar properties) and then `face` (one list property of three indices per face)."""
     with open(filename, 'rb') as f:
         if f.readline().strip() != b'ply':
             raise ValueError(f'{filename}: not a PLY file')
@@ -186,15 +220,18 @@ def read_ply_mesh(filename):
             order = '<' if fmt == 'binary_little_endian' else '>'
             dt = np.dtype([(p[1], order + _PLY_TYPES[p[0]]) for p in props])
             data = np.frombuffer(f.read(dt.itemsize * n), dtype=dt, count=n)
-            col = {k: data[k].astype(np.float64) for k in names}
+            col = {k: data[k] for k in names}
             ft = np.dtype([('n', order + _PLY_TYPES[fprops[0][1]]), ('v', order + _PLY_TYPES[fprops[0][2]], 3)])
             faces = np.frombuffer(f.read(ft.itemsize * nf), dtype=ft, count=nf)
             if (faces['n'] != 3).any():
                 raise ValueError(f'{filename}: only triangles are supported')
             tri = faces['v'].astype(np.int32).reshape(nf, 3)
-    out = {'xyz': np.stack([col[k] for k in 'xyz'], 1), 'triangles': tri}
+    out = {'xyz': np.stack([col[k].astype(np.float64) for k in 'xyz'], 1), 'triangles': tri}
     if all(k in col for k in ('nx', 'ny', 'nz')):
-        out['normals'] = np.stack([col[k] for k in ('nx', 'ny', 'nz')], 1)
+        out['normals'] = np.stack([col[k].astype(np.float64) for k in ('nx', 'ny', 'nz')], 1)
+    colors = _ply_colors(col)
+    if colors is not None:
+        out['colors'] = colors
     return out
 
 
@@ -217,7 +254,7 @@ def load_cloud(filename):
     raise ValueError(f'unrecognised point-cloud file type: {filename}')
 
 
-# ---- PNG (grayscale depth images) -----------------------------------------------------------------------
+# ---- PNG (grayscale depth images, RGB colour images) -----------------------------------------------------
 _PNG_MAGIC = b'\x89PNG\r\n\x1a\n'
 
 
@@ -226,18 +263,14 @@ def _png_chunk(tag, data):
     return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
 
 
-def write_png_gray16(filename, image, filter_type=0):
-    """A [H,W] uint16 image as a 16-bit grayscale PNG (the 3DMatch depth format; stdlib zlib only).  Every scanline is
-    written with `filter_type` (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth); readers must accept all five."""
+def _png_write(filename, raw, bpp, width, bit_depth, colour, filter_type):
+    """`raw` uint8 [H, W bpp], the image's bytes as PNG orders them, as a non-interlaced PNG of one IDAT chunk whose every
+    scanline is written with `filter_type` (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth; stdlib zlib only)."""
     import zlib
-    img = np.asarray(image)
-    if img.ndim != 2 or img.dtype != np.uint16:
-        raise ValueError(f'expected a [H,W] uint16 image, got {img.dtype} {img.shape}')
     if filter_type not in (0, 1, 2, 3, 4):
         raise ValueError(f'PNG filter type {filter_type}')
-    h, w = img.shape
-    raw = img.astype('>u2').view(np.uint8).reshape(h, w * 2).astype(np.int32)
-    bpp = 2
+    raw = raw.astype(np.int32)
+    h = len(raw)
     left = np.zeros_like(raw)
     left[:, bpp:] = raw[:, :-bpp]
     up = np.zeros_like(raw)
@@ -256,19 +289,40 @@ def write_png_gray16(filename, image, filter_type=0):
         p = left + up - upleft
         pa, pb, pc = np.abs(p - left), np.abs(p - up), np.abs(p - upleft)
         pred = np.where((pa <= pb) & (pa <= pc), left, np.where(pb <= pc, up, upleft))
-    rows = np.empty((h, 1 + w * 2), np.uint8)
+    rows = np.empty((h, 1 + raw.shape[1]), np.uint8)
     rows[:, 0] = filter_type
     rows[:, 1:] = ((raw - pred) & 0xff).astype(np.uint8)
     with open(filename, 'wb') as f:
         f.write(_PNG_MAGIC)
-        f.write(_png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 16, 0, 0, 0, 0)))
+        f.write(_png_chunk(b'IHDR', struct.pack('>IIBBBBB', width, h, bit_depth, colour, 0, 0, 0)))
         f.write(_png_chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)))
         f.write(_png_chunk(b'IEND', b''))
 
 
-def read_png_gray(filename):
-    """A non-interlaced grayscale PNG of 8 or 16 bits as [H,W] uint8 / uint16 (what `o3d.io.read_image` gives for a
-    depth file), all five scanline filters.  Other colour types, bit depths and interlacing raise ValueError."""
+def write_png_gray16(filename, image, filter_type=0):
+    """A [H,W] uint16 image as a 16-bit grayscale PNG (the 3DMatch depth format; stdlib zlib only).  Every scanline is
+    written with `filter_type` (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth); readers must accept all five."""
+    img = np.asarray(image)
+    if img.ndim != 2 or img.dtype != np.uint16:
+        raise ValueError(f'expected a [H,W] uint16 image, got {img.dtype} {img.shape}')
+    h, w = img.shape
+    _png_write(filename, img.astype('>u2').view(np.uint8).reshape(h, w * 2), 2, w, 16, 0, filter_type)
+
+
+def write_png_rgb8(filename, image, filter_type=0):
+    """A [H,W,3] uint8 image (R, G, B) as an 8-bit RGB PNG (colour type 2: the 3DMatch colour format), every scanline
+    written with `filter_type` as in `write_png_gray16`."""
+    img = np.asarray(image)
+    if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
+        raise ValueError(f'expected a [H,W,3] uint8 image, got {img.dtype} {img.shape}')
+    h, w = img.shape[:2]
+    _png_write(filename, np.ascontiguousarray(img).reshape(h, w * 3), 3, w, 8, 2, filter_type)
+
+
+def _png_scanlines(filename, bytes_per_pixel, supported):
+    """(width, height, bit depth, colour type, uint8 [H, W bpp]: the unfiltered scanlines) of a non-interlaced PNG.
+    `bytes_per_pixel` maps the (colour type, bit depth) pairs the caller reads to their bpp; `supported` names them in the
+    ValueError every other PNG gets.  All five scanline filters."""
     import zlib
     with open(filename, 'rb') as f:
         data = f.read()
@@ -290,10 +344,10 @@ def read_png_gray(filename):
     if hdr is None:
         raise ValueError(f'{filename}: PNG without IHDR')
     w, h, depth, colour, comp, filt, interlace = hdr
-    if colour != 0 or depth not in (8, 16) or interlace != 0 or comp != 0 or filt != 0:
-        raise ValueError(f'{filename}: only non-interlaced 8/16-bit grayscale PNG is supported '
+    if (colour, depth) not in bytes_per_pixel or interlace != 0 or comp != 0 or filt != 0:
+        raise ValueError(f'{filename}: only {supported} is supported '
                          f'(colour type {colour}, bit depth {depth}, interlace {interlace})')
-    bpp = depth // 8
+    bpp = bytes_per_pixel[(colour, depth)]
     stride = w * bpp
     raw = np.frombuffer(zlib.decompress(b''.join(idat)), np.uint8)
     if raw.size != h * (stride + 1):
@@ -332,6 +386,20 @@ def read_png_gray(filename):
             raise ValueError(f'{filename}: PNG filter type {ft}')
         out[y] = cur.astype(np.uint8)
         prev = cur
+    return w, h, depth, colour, out
+
+
+def read_png_gray(filename):
+    """A non-interlaced grayscale PNG of 8 or 16 bits as [H,W] uint8 / uint16 (what `o3d.io.read_image` gives for a
+    depth file), all five scanline filters.  Other colour types, bit depths and interlacing raise ValueError."""
+    w, h, depth, _, out = _png_scanlines(filename, {(0, 8): 1, (0, 16): 2}, 'non-interlaced 8/16-bit grayscale PNG')
     if depth == 8:
         return out
     return out.view('>u2').astype(np.uint16).reshape(h, w)
+
+
+def read_png_rgb8(filename):
+    """A non-interlaced 8-bit PNG of colour type 2 (RGB) or 6 (RGBA, the alpha dropped) as [H,W,3] uint8 (what
+    `o3d.io.read_image` gives for a 3DMatch colour file), all five scanline filters.  Anything else raises ValueError."""
+    w, h, _, colour, out = _png_scanlines(filename, {(2, 8): 3, (6, 8): 4}, 'non-interlaced 8-bit RGB / RGBA PNG')
+    return np.ascontiguousarray(out.reshape(h, w, 4 if colour == 6 else 3)[:, :, :3])

@@ -797,8 +797,29 @@ def check_tsdf_args(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale
     return intrinsic, pose.reshape(F, 16), extrinsic.reshape(F, 16), (F, H, W)
 
 
+TSDF_COLOR_MAX_FRAMES = 8421504   # DGR_TSDF_COLOR_MAX_FRAMES: 255 F fits an int32
+
+
+def check_tsdf_color_args(color, depth):
+    """The `color` argument of `tsdf_fragment` against its (already checked) `depth`.  ValueError for a `color` that is not
+    uint8, not `depth`'s [F,H,W] with a last axis of 3, a tensor on another device than a `depth` that is a tensor, more than
+    TSDF_COLOR_MAX_FRAMES frames (a voxel's colour sum could pass 2^31).  Only `dtype`, `shape` and (of tensors) `device` are
+    looked at: nothing touches the device."""
+    if not (hasattr(color, 'dtype') and hasattr(color, 'shape')):
+        raise ValueError('color must be a numpy array or a torch tensor')
+    if str(color.dtype).replace('torch.', '') != 'uint8':
+        raise ValueError(f'color must be uint8, got {color.dtype}')
+    want = tuple(int(v) for v in depth.shape) + (3,)
+    if tuple(int(v) for v in color.shape) != want:
+        raise ValueError(f'color must be [F,H,W,3] = {list(want)} like depth, got {list(color.shape)}')
+    if torch.is_tensor(color) and torch.is_tensor(depth) and color.device != depth.device:
+        raise ValueError(f'color is on {color.device}, depth on {depth.device}')
+    if want[0] > TSDF_COLOR_MAX_FRAMES:
+        raise ValueError(f'{want[0]} frames with colour: at most {TSDF_COLOR_MAX_FRAMES} (255 F must fit an int32)')
+
+
 def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1000.0, depth_trunc=4.5, block=16, stride=4,
-                  min_weight=1, return_volume=False, return_stats=False):
+                  min_weight=1, return_volume=False, return_stats=False, color=None):
     """TSDF fusion of F depth frames under their camera poses and the surface points of the fused volume
     (dgr_tsdf_fragment; what the reference's util/integration.py does with Open3D's ScalableTSDFVolume).  depth uint16
     [F,H,W] (numpy or a device tensor), intrinsic = (fx, fy, cx, cy), pose [F,4,4] float64 camera-to-world as the
@@ -809,9 +830,15 @@ def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1
     +y, +z edges whose two ends have at least `min_weight` observations.
     Returns xyz float64 [P,3] on the device; with `return_volume` a dict with `xyz`, `blocks` int32 [nb,3], `tsdf`
     float32 [nb, block^3] and `weight` int32 [nb, block^3]; with `return_stats` the dict also has `kept`, the (block,
-    frame) pairs the integration did not cull.  Two calls agree bit for bit."""
+    frame) pairs the integration did not cull.  Two calls agree bit for bit.
+    `color` uint8 [F,H,W,3] (R, G, B; numpy or a tensor on `depth`'s device) is fused with the depth (dgr_tsdf_fragment_rgb):
+    a voxel sums the colour of every pixel that updates it, a point gets the two ends' mean colours blended as its position
+    is.  The result is then always a dict: `xyz`, `color` float64 [P,3] in [0, 1], with `return_volume` also `rgb_sum`
+    int32 [nb, block^3, 3]; `xyz`, `blocks`, `tsdf` and `weight` are exactly those of the call without `color`."""
     intrinsic, pose, extrinsic, (F, H, W) = check_tsdf_args(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale,
                                                             depth_trunc, block, stride, min_weight)
+    if color is not None:
+        check_tsdf_color_args(color, depth)
     lib = _lib.load()
     if torch.is_tensor(depth):
         _dev(depth)
@@ -819,23 +846,36 @@ def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1
     else:
         # torch has no arithmetic on uint16 and older versions no uint16 at all: the bytes travel as int16
         a = np.ascontiguousarray(depth)
-        d = torch.from_numpy((a if a.flags.writeable else a.copy()).view(np.int16)).cuda()
+        d = torch.from_numpy((a if a.flags.writeable else a.copy()).view(np.int16))
+        d = d.to(color.device) if torch.is_tensor(color) and color.is_cuda else d.cuda()
     dev = d.device
+    if torch.is_tensor(color):
+        _dev(color)
+        col = color.contiguous()
+    elif color is not None:
+        a = np.ascontiguousarray(color)
+        col = torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
     V = block ** 3
     max_points, max_blocks = TSDF_FIRST_POINTS, TSDF_FIRST_BLOCKS
     nb, npts, kept = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     while True:
         xyz = torch.empty((max_points, 3), dtype=torch.float64, device=dev)
-        blocks = tsdf = weight = None
+        blocks = tsdf = weight = rgb_sum = pcolor = None
         if return_volume:
             blocks = torch.empty((max_blocks, 3), dtype=torch.int32, device=dev)
             tsdf = torch.empty((max_blocks, V), dtype=torch.float32, device=dev)
             weight = torch.empty((max_blocks, V), dtype=torch.int32, device=dev)
-        rc = lib.dgr_tsdf_fragment(get_ctx(dev), ptr(d), F, H, W, _np_ptr(intrinsic), _np_ptr(pose), _np_ptr(extrinsic),
-                                   float(voxel_length), float(sdf_trunc), float(depth_scale), float(depth_trunc), int(block),
-                                   int(stride), int(min_weight), ptr(xyz), max_points, ptr(blocks), ptr(tsdf), ptr(weight),
-                                   max_blocks if return_volume else 0, C.byref(nb), C.byref(npts),
-                                   C.byref(kept) if return_stats else None, stream_ptr(dev.index))
+        args = (get_ctx(dev), ptr(d), F, H, W, _np_ptr(intrinsic), _np_ptr(pose), _np_ptr(extrinsic), float(voxel_length),
+                float(sdf_trunc), float(depth_scale), float(depth_trunc), int(block), int(stride), int(min_weight), ptr(xyz),
+                max_points, ptr(blocks), ptr(tsdf), ptr(weight), max_blocks if return_volume else 0, C.byref(nb),
+                C.byref(npts), C.byref(kept) if return_stats else None)
+        if color is None:
+            rc = lib.dgr_tsdf_fragment(*args, stream_ptr(dev.index))
+        else:
+            pcolor = torch.empty((max_points, 3), dtype=torch.float64, device=dev)
+            if return_volume:
+                rgb_sum = torch.empty((max_blocks, V, 3), dtype=torch.int32, device=dev)
+            rc = lib.dgr_tsdf_fragment_rgb(*args, ptr(col), ptr(rgb_sum), ptr(pcolor), stream_ptr(dev.index))
         # the one recoverable failure: an output array too small for what the call found -- it says how much it needs
         if rc == _lib.DGR_ENOMEM and ((return_volume and nb.value > max_blocks) or npts.value > max_points):
             max_blocks, max_points = max(max_blocks, nb.value), max(max_points, npts.value)
@@ -843,11 +883,15 @@ def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1
         check(rc)
         break
     xyz = xyz[:npts.value]
-    if not (return_volume or return_stats):
+    if not (return_volume or return_stats or color is not None):
         return xyz
     out = {'xyz': xyz}
+    if color is not None:
+        out['color'] = pcolor[:npts.value]
     if return_volume:
         out.update(blocks=blocks[:nb.value], tsdf=tsdf[:nb.value], weight=weight[:nb.value])
+        if color is not None:
+            out['rgb_sum'] = rgb_sum[:nb.value]
     if return_stats:
         out.update(kept=int(kept.value), n_blocks=int(nb.value))
     return out
@@ -856,6 +900,15 @@ def tsdf_fragment(depth, intrinsic, pose, voxel_length, sdf_trunc, depth_scale=1
 # ----------------------------------------------------------------------------
 # triangle mesh and vertex normals of a fused TSDF volume (csrc/tsdfmesh.hip)
 TSDF_MESH_FIRST_VERTICES, TSDF_MESH_FIRST_TRIANGLES = 1 << 20, 1 << 21   # tsdf_mesh's first output arrays; it asks again when they are small
+
+
+def check_tsdf_mesh_color_args(rgb_sum, tsdf):
+    """The `rgb_sum` argument of `tsdf_mesh` against its (already checked) `tsdf`: ValueError unless it is an int32 tensor
+    [nb, block^3, 3] on `tsdf`'s device.  Nothing touches the device."""
+    if not torch.is_tensor(rgb_sum) or rgb_sum.device != tsdf.device:
+        raise ValueError("rgb_sum must be a tensor on tsdf's device")
+    if rgb_sum.dtype != torch.int32 or tuple(rgb_sum.shape) != tuple(tsdf.shape) + (3,):
+        raise ValueError(f'rgb_sum must be int32 {list(tsdf.shape) + [3]}, got {rgb_sum.dtype} {list(rgb_sum.shape)}')
 
 
 def check_tsdf_mesh_args(blocks, tsdf, weight, voxel_length, block=16, min_weight=1):
@@ -883,14 +936,19 @@ def check_tsdf_mesh_args(blocks, tsdf, weight, voxel_length, block=16, min_weigh
     return nb, voxel_length, block, min_weight
 
 
-def tsdf_mesh(blocks, tsdf, weight, voxel_length, block=16, min_weight=1, normals=True):
+def tsdf_mesh(blocks, tsdf, weight, voxel_length, block=16, min_weight=1, normals=True, rgb_sum=None):
     """Triangle mesh and vertex normals of a fused TSDF volume (dgr_tsdf_mesh; Open3D's extract_triangle_mesh in the
     reference's util/integration.py).  blocks int32 [nb,3], tsdf float32 [nb, block^3], weight int32 [nb, block^3]: device
     tensors as `tsdf_fragment(..., return_volume=True)` returns them, or a volume made by hand in that layout.
     Returns a dict of device tensors: `xyz` float64 [P,3] -- the very points of `tsdf_fragment`, in its order --, `normal`
     float64 [P,3] (unit, from negative to positive; absent without `normals`) and `triangles` int32 [T,3], wound so that
-    they face the positive side.  Two calls agree bit for bit."""
+    they face the positive side.  Two calls agree bit for bit.  With `rgb_sum` int32 [nb, block^3, 3], the colour sums of
+    `tsdf_fragment(..., color=..., return_volume=True)`, also `color` float64 [P,3] in [0, 1]: the very colours of that call's
+    points (dgr_tsdf_mesh_rgb); the rest of the dict is what it is without `rgb_sum`."""
     nb, voxel_length, block, min_weight = check_tsdf_mesh_args(blocks, tsdf, weight, voxel_length, block, min_weight)
+    if rgb_sum is not None:
+        check_tsdf_mesh_color_args(rgb_sum, tsdf)
+        rgb_sum = rgb_sum.contiguous()
     lib = _lib.load()
     dev = blocks.device
     blocks, tsdf, weight = blocks.contiguous(), tsdf.contiguous(), weight.contiguous()
@@ -900,8 +958,13 @@ def tsdf_mesh(blocks, tsdf, weight, voxel_length, block=16, min_weight=1, normal
         xyz = torch.empty((max_v, 3), dtype=torch.float64, device=dev)
         normal = torch.empty((max_v, 3), dtype=torch.float64, device=dev) if normals else None
         tri = torch.empty((max_t, 3), dtype=torch.int32, device=dev)
-        rc = lib.dgr_tsdf_mesh(get_ctx(dev), ptr(blocks), nb, ptr(tsdf), ptr(weight), block, voxel_length, min_weight,
-                               ptr(xyz), ptr(normal), max_v, ptr(tri), max_t, C.byref(nv), C.byref(nt), stream_ptr(dev.index))
+        args = (get_ctx(dev), ptr(blocks), nb, ptr(tsdf), ptr(weight), block, voxel_length, min_weight, ptr(xyz), ptr(normal),
+                max_v, ptr(tri), max_t, C.byref(nv), C.byref(nt))
+        if rgb_sum is None:
+            rc = lib.dgr_tsdf_mesh(*args, stream_ptr(dev.index))
+        else:
+            vcolor = torch.empty((max_v, 3), dtype=torch.float64, device=dev)
+            rc = lib.dgr_tsdf_mesh_rgb(*args, ptr(rgb_sum), ptr(vcolor), stream_ptr(dev.index))
         # the one recoverable failure: an output array too small -- the call says how much both need
         if rc == _lib.DGR_ENOMEM and (nv.value > max_v or nt.value > max_t):
             max_v, max_t = max(max_v, nv.value), max(max_t, nt.value)
@@ -911,6 +974,8 @@ def tsdf_mesh(blocks, tsdf, weight, voxel_length, block=16, min_weight=1, normal
     out = {'xyz': xyz[:nv.value], 'triangles': tri[:nt.value]}
     if normals:
         out['normal'] = normal[:nv.value]
+    if rgb_sum is not None:
+        out['color'] = vcolor[:nv.value]
     return out
 
 

@@ -247,7 +247,7 @@ def gt_correspondences(xyz0, xyz1, T_gt, voxel_size, frac=0.5, seed=0):
 
 
 # ----------------------------------------------------------------------------
-# RGB-D sequences (depth only) for the TSDF front end
+# RGB-D sequences for the TSDF front end
 # ----------------------------------------------------------------------------
 def synth_rgbd(seed, n_frames, width, height, focal, sweep_deg=40.0, radius=0.5, cam_height=0.3):
     """A depth sequence of `_indoor_scene`'s recipe (a 4 x 3.5 x 2.6 m room with six cuboids on its floor), ray-cast
@@ -302,16 +302,51 @@ def synth_rgbd(seed, n_frames, width, height, focal, sweep_deg=40.0, radius=0.5,
     return depth, (fx, fy, cx, cy), poses, boxes
 
 
-def write_rgbd_sequence(directory, depth, intrinsic, poses):
+def color_texture(points, seed=0):
+    """uint8 [N,3]: the procedural texture of `synth_color` at world points [N,3] -- per channel e
+    rint(127.5 + 100 sin(k_e . p + phi_e)), k_e a seeded direction times 2 pi / wavelength with a wavelength in [1, 2] m,
+    phi_e a seeded phase.  A function of the world point alone, so every view of a surface point sees one colour."""
+    rng = np.random.default_rng([int(seed), 0xC0102])
+    k = rng.standard_normal((3, 3))
+    k *= (2 * np.pi / rng.uniform(1.0, 2.0, size=3) / np.linalg.norm(k, axis=1))[:, None]
+    phi = rng.uniform(0, 2 * np.pi, size=3)
+    return np.rint(127.5 + 100.0 * np.sin(np.asarray(points, np.float64) @ k.T + phi)).astype(np.uint8)
+
+
+def synth_color(depth, intrinsic, poses, seed=0):
+    """uint8 [F,H,W,3] colour images for a depth sequence (`synth_rgbd`'s, or any): every valid pixel (raw > 0) is
+    back-projected to the world under its frame's pose (depth in millimetres) and gets `color_texture` there; invalid
+    pixels get 0.  View-consistent up to the depth's rounding to millimetres."""
+    depth = np.asarray(depth)
+    F, H, W = depth.shape
+    fx, fy, cx, cy = (float(v) for v in intrinsic)
+    xn = ((np.arange(W) - cx) / fx)[None, :]
+    yn = ((np.arange(H) - cy) / fy)[:, None]
+    out = np.zeros((F, H, W, 3), np.uint8)
+    for f in range(F):
+        d = depth[f].astype(np.float64) / 1000.0
+        pc = np.stack([xn * d, yn * d, d], -1).reshape(-1, 3)
+        M = np.asarray(poses[f], np.float64)
+        pw = pc @ M[:3, :3].T + M[:3, 3]
+        out[f] = np.where((depth[f] > 0)[..., None], color_texture(pw, seed).reshape(H, W, 3), 0)
+    return out
+
+
+def write_rgbd_sequence(directory, depth, intrinsic, poses, color=None):
     """Writes a sequence in the 3DMatch raw layout the reference's util/integration.py reads: `frame-%06d.depth.png`
     (16-bit grayscale, millimetres), `frame-%06d.pose.txt` (4x4 camera-to-world) and `intrinsics.txt` (3x3 K) in
-    `directory`.  No colour images: the TSDF front end ignores them.  Returns the number of frames."""
+    `directory`; with `color` uint8 [F,H,W,3] (`synth_color`'s) also `frame-%06d.color.png` (8-bit RGB), which
+    `util.integration.process_seq(..., color=True)` fuses with the depth.  Returns the number of frames."""
     import os
-    from .eval.formats import write_png_gray16
+    from .eval.formats import write_png_gray16, write_png_rgb8
+    if color is not None and (np.asarray(color).shape != tuple(depth.shape) + (3,) or np.asarray(color).dtype != np.uint8):
+        raise ValueError(f'color must be uint8 {list(depth.shape) + [3]}, got {np.asarray(color).dtype} {list(np.shape(color))}')
     os.makedirs(directory, exist_ok=True)
     fx, fy, cx, cy = intrinsic
     np.savetxt(os.path.join(directory, 'intrinsics.txt'), np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]]), fmt='%.17g')
     for f in range(len(depth)):
         write_png_gray16(os.path.join(directory, 'frame-%06d.depth.png' % f), depth[f])
+        if color is not None:
+            write_png_rgb8(os.path.join(directory, 'frame-%06d.color.png' % f), color[f])
         np.savetxt(os.path.join(directory, 'frame-%06d.pose.txt' % f), np.asarray(poses[f], np.float64), fmt='%.17g')
     return len(depth)

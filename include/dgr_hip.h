@@ -575,6 +575,30 @@ int dgr_tsdf_fragment(dgr_ctx *ctx, const uint16_t *depth, int nframes, int heig
                       int64_t max_points, int32_t *blocks_out, float *tsdf_out, int32_t *weight_out, int64_t max_blocks,
                       int64_t *n_blocks_out, int64_t *n_points_out, int64_t *kept_out, dgr_stream stream);
 
+/* The same fusion with colour (the reference builds its volume with color_type RGB8 and feeds it the *.color.png of every
+ * depth frame): dgr_tsdf_fragment's arguments, contract and results -- blocks, tsdf, weight and the points are EXACTLY what
+ * the call without colour gives -- plus color dev uint8 [F,H,W,3] (R, G, B), the same F, H, W as depth.  Open3D keeps a
+ * running floating-point mean per voxel; this library keeps exact integer sums: the same mean, free of the frame order.
+ * The statement is this library's own, not a claim about Open3D's roundings; tests/tsdf_color_ref.py is its numpy form.
+ *   integration  every voxel carries rgb_sum i32 [3] = 0 beside tsdf / weight; whenever frame f updates the voxel's tsdf from
+ *                pixel (u, v) -- the same condition, the same pixel -- rgb_sum[e] += color[f, v, u, e], e = 0, 1, 2
+ *   colours      the point on edge (i0, a) with far end i1 and r = |f0| / (|f0| + |f1|), the very r that places it:
+ *                m0[e] = (double)rgb_sum0[e] / (double)w0, m1 likewise; c[e] = (m0[e] + r (m1[e] - m0[e])) / 255.0, float64
+ *                without fma, every step one correctly rounded operation in the order written.  w0, w1 >= min_weight >= 1.
+ *                Only the two usable ends of a crossing are read: no other voxel's rgb_sum reaches an output
+ * Outputs: rgb_sum_out dev i32 [max_blocks, block^3, 3] goes together with blocks_out, tsdf_out, weight_out: all four or none;
+ * point_color_out dev f64 [max_points,3] in [0, 1] (NULL: not computed).  On DGR_ENOMEM for the points nothing is written to
+ * point_color_out either.  The call synchronises twice, like dgr_tsdf_fragment, and adds no atomics.
+ * DGR_EINVAL before any device work, beyond dgr_tsdf_fragment's: color NULL, rgb_sum_out without the other three volume
+ * outputs or they without it, F > DGR_TSDF_COLOR_MAX_FRAMES (255 F must fit an int32). */
+#define DGR_TSDF_COLOR_MAX_FRAMES 8421504
+int dgr_tsdf_fragment_rgb(dgr_ctx *ctx, const uint16_t *depth, int nframes, int height, int width, const double *intrinsic,
+                          const double *pose, const double *extrinsic, double voxel_length, double sdf_trunc,
+                          double depth_scale, double depth_trunc, int block, int stride, int min_weight, double *xyz_out,
+                          int64_t max_points, int32_t *blocks_out, float *tsdf_out, int32_t *weight_out, int64_t max_blocks,
+                          int64_t *n_blocks_out, int64_t *n_points_out, int64_t *kept_out, const uint8_t *color,
+                          int32_t *rgb_sum_out, double *point_color_out, dgr_stream stream);
+
 /* Triangle mesh and vertex normals of a fused TSDF volume (csrc/tsdfmesh.hip): what the reference's util/integration.py gets
  * from Open3D's volume.extract_triangle_mesh().  Open3D is absent here: triangulation and roundings below are this library's
  * own statement, and tests/tsdf_mesh_ref.py is the same statement in numpy, compared bit for bit.
@@ -611,6 +635,17 @@ int dgr_tsdf_mesh(dgr_ctx *ctx, const int32_t *blocks, int64_t n_blocks, const f
                   double voxel_length, int min_weight, double *xyz_out, double *normal_out, int64_t max_vertices,
                   int32_t *tri_out, int64_t max_triangles, int64_t *n_vertices_out, int64_t *n_triangles_out,
                   dgr_stream stream);
+
+/* The same mesh with vertex colours: dgr_tsdf_mesh's arguments, contract and results plus rgb_sum dev i32 [n_blocks, block^3, 3],
+ * the colour sums dgr_tsdf_fragment_rgb returns beside tsdf / weight, and color_out dev f64 [max_vertices,3]: the colour of
+ * vertex k by the formula stated at dgr_tsdf_fragment_rgb -- point k's colour there, the same bits (one text computes both).
+ * Only the rgb_sum of the two usable ends of a crossing is read.  Nothing is written to color_out on DGR_ENOMEM or on an
+ * error found on the device.  DGR_EINVAL before any device work, beyond dgr_tsdf_mesh's: rgb_sum NULL with n_blocks > 0,
+ * color_out NULL with max_vertices > 0. */
+int dgr_tsdf_mesh_rgb(dgr_ctx *ctx, const int32_t *blocks, int64_t n_blocks, const float *tsdf, const int32_t *weight, int block,
+                      double voxel_length, int min_weight, double *xyz_out, double *normal_out, int64_t max_vertices,
+                      int32_t *tri_out, int64_t max_triangles, int64_t *n_vertices_out, int64_t *n_triangles_out,
+                      const int32_t *rgb_sum, double *color_out, dgr_stream stream);
 
 /* ---- debug entry points (parity tests): the device functions of the registration kernel on their own.
  * ortho2rotation (core/registration.py:16-64) forward for n parameter rows p6 [n,6] -> R9_out [n,9] (row-major 3x3) and,

@@ -10,6 +10,13 @@ volume, the two results compared for exact equality.  The one condition: there t
 
     python tools/tsdf_mesh_bench.py [--reps 20] [--out profiles/tsdf_mesh_bench.json] [--commit HASH]
     python tools/tsdf_mesh_bench.py --profile-only     # three calls per block size and nothing else: what a kernel trace wraps
+
+The colour leg (`--color`): per block size the mesh call with and without `rgb_sum=` on the volume fused
+from the same frames with `synth_color` images, the vertex colours compared with the fragment's point colours bit for bit,
+and the median / maximum |vertex colour - texture at the vertex| in levels of 255 (information only).  The record goes
+into the output file beside tools/tsdf_bench.py's, under `mesh`.
+
+    python tools/tsdf_mesh_bench.py --color [--reps 20] [--out profiles/tsdf_color_bench.json]
 """
 import argparse
 import json
@@ -33,6 +40,7 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--commit', default=None)
     ap.add_argument('--profile-only', action='store_true')
+    ap.add_argument('--color', action='store_true', help='the colour leg instead (see the module docstring)')
     a = ap.parse_args()
     from deepglobalregistration_amd import ops, synth
     import tsdf_cases
@@ -42,6 +50,31 @@ def main():
         raise SystemExit('tsdf_mesh_bench measures on the GPU; there is nothing to time without one')
     depth, K, poses, _ = synth.synth_rgbd(0, FRAMES, WIDTH, HEIGHT, FOCAL, sweep_deg=SWEEP)
     depth_dev = torch.from_numpy(depth).cuda()
+    if a.color:
+        color = synth.synth_color(depth, K, poses, seed=0)
+        color_dev = torch.from_numpy(color).cuda()
+        rec = {'commit': a.commit or commit_stamp(), 'device': torch.cuda.get_device_name(0), 'reps': a.reps}
+        for block in (8, 16):
+            vol = ops.tsdf_fragment(depth_dev, K, poses, VOXEL, TRUNC, block=block, stride=STRIDE, return_volume=True, color=color_dev)
+
+            def mesh(rgb_sum=None):
+                return ops.tsdf_mesh(vol['blocks'], vol['tsdf'], vol['weight'], VOXEL, block=block, rgb_sum=rgb_sum)
+            m = mesh(vol['rgb_sum'])
+            if not torch.equal(m['color'].view(torch.int64), vol['color'].view(torch.int64)):
+                raise SystemExit(f"block {block}: the vertex colours are not the fragment's point colours")
+            err = np.abs(255.0 * m['color'].cpu().numpy() - synth.color_texture(m['xyz'].cpu().numpy(), 0).astype(np.float64))
+            rec[f'block{block}'] = {'vertices': len(m['xyz']), 'triangles': len(m['triangles']), 'mesh_ms': timed(mesh, a.reps),
+                                    'mesh_color_ms': timed(lambda: mesh(vol['rgb_sum']), a.reps),
+                                    'texture_error_levels': {'median': float(np.median(err)), 'max': float(err.max())}}
+            del m, vol
+        out = json.load(open(a.out)) if a.out and os.path.exists(a.out) else {}
+        out['mesh'] = rec
+        print(json.dumps(rec, indent=1))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                json.dump(out, f, indent=1)
+        return
     out = {'commit': a.commit or commit_stamp(), 'device': torch.cuda.get_device_name(0), 'reps': a.reps,
            'input': {'width': WIDTH, 'height': HEIGHT, 'focal': FOCAL, 'frames': FRAMES, 'sweep_deg': SWEEP, 'voxel_length': VOXEL,
                      'sdf_trunc': TRUNC, 'stride': STRIDE}}
