@@ -172,10 +172,15 @@ struct DgrMapSet {
   int32_t *overflow = nullptr;  // device flag: kernel-map capacity exceeded / duplicate coords
 };
 
+// What dgr_build_maps builds.  lean: the kernel maps keep only what the network forward reads (kmap.hip, map_keep).
+// tables (D = 3): dense neighbour tables; with lean nothing else -- conv1 runs fused with its search, of any kernel
+// size --, without lean the rule-major maps too.  lists (lean, tables): rule-major lists of the coarse tables as well.
+struct DgrMapsMode {
+  bool lean, tables, lists;
+};
 // Builds all coordinate maps and kernel maps of one sparse tensor into `arena`.
 int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int conv1_ks,
-                   DgrMapSet *ms, hipStream_t stream, bool skip_conv1_map = false, bool lean = false,
-                   bool nbr_tables = false, bool nbr_lists = false);
+                   DgrMapSet *ms, hipStream_t stream, DgrMapsMode mode);
 // per-offset pair counts of a neighbour table (statistics / tests; synchronises)
 int dgr_nbr_counts(const DgrNbrTable &t, const int32_t *n_out_dev, int64_t counts[27]);
 // conv1 fused with its neighbour search (D = 3, Cin <= 8, Cout = 32): no kernel map for the ks^3 offsets

@@ -86,28 +86,25 @@ __device__ __forceinline__ int mask_rank(const uint32_t *__restrict__ m, int k) 
   return r + __popc(m[w] & ((1u << (k & 31)) - 1u));
 }
 
-// wpre (optional): pairs of the row in the mask words before word i (a row can have all K = 729 offsets: 16 bits)
 __global__ void mask_count_kernel(const uint32_t *__restrict__ mask, int KW, const int32_t *n_dev, int64_t n_cap,
-                                  int32_t *__restrict__ cnt, unsigned short *__restrict__ wpre = nullptr) {
+                                  int32_t *__restrict__ cnt) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_cap) return;
   int c = 0;
   if (r < *n_dev)
-    for (int i = 0; i < KW; ++i) {
-      if (wpre) wpre[r * KW + i] = (unsigned short)c;
-      c += __popc(mask[r * KW + i]);
-    }
+    for (int i = 0; i < KW; ++i) c += __popc(mask[r * KW + i]);
   cnt[r] = c;
 }
-// the same for up to KM_JOBS6 bit matrices in ONE launch (blockIdx.y = matrix), the row's words requested together (the
-// loop above alternates loads and stores: 23 dependent round trips per row; three launches of 30 us per 6-D forward)
-constexpr int KM_MC_JOBS = 8;
+// the same for the bit matrices of the input rows of the three strided 6-D maps in ONE launch (blockIdx.y = matrix), the
+// row's words requested together (a loop that alternates loads and stores: 23 dependent round trips per row), plus
+// wpre: pairs of the row in the mask words before word i (a row can have all K = 729 offsets: 16 bits)
+constexpr int KM_MAXJOBS = 8;   // kernel maps per multi-map launch (blockIdx.y = map): the 6-D builder passes seven
 struct MaskCountJobs {
-  const uint32_t *mask[KM_MC_JOBS];
-  const int32_t *n_dev[KM_MC_JOBS];
-  long long n_cap[KM_MC_JOBS];
-  int32_t *cnt[KM_MC_JOBS];
-  unsigned short *wpre[KM_MC_JOBS];
+  const uint32_t *mask[KM_MAXJOBS];
+  const int32_t *n_dev[KM_MAXJOBS];
+  long long n_cap[KM_MAXJOBS];
+  int32_t *cnt[KM_MAXJOBS];
+  unsigned short *wpre[KM_MAXJOBS];
 };
 template <int KW>
 __global__ void mask_count_multi(MaskCountJobs J) {
@@ -163,7 +160,9 @@ __device__ __forceinline__ unsigned long long hit_pack(int k, int64_t o, int64_t
 // wave and places its pairs directly (positions depend on the bit matrix only).  Arena per output row: 0.9 KB
 // (symmetric maps) / 1.7 KB (strided maps).
 constexpr int KM_REGION = 512;
-constexpr int KM_JOBS6 = 8;   // kernel maps per multi-job launch of the 6-D builder (blockIdx.y = map)
+// (a wave = 64 rows under one first-half offset: a dozen records at the fine levels and in the strided maps, ~180 in
+// the stride-8 map with its 39 neighbours per row, several times that in its dense corners)
+constexpr int km_region_of(int ts_in, bool symmetric) { return (ts_in >= 8 && symmetric) ? 2 * KM_REGION : KM_REGION / 2; }
 struct HitList {
   unsigned long long *recs;   // [waves][region]
   int32_t *wave_count;        // [waves]; -1: the region overflowed, replay the wave
@@ -256,23 +255,41 @@ __device__ __forceinline__ void pruned_search6(const PrunedArgs &a, int64_t t, E
   }
 }
 
+// Everything the three kernels of the 6-D builder (search, transposing pass, placing pass) need of ONE map; the host
+// fills the record once (build_kernel_maps6) and every kernel takes all records by value, blockIdx.y = map, and reads
+// the fields it uses from its map's record.
+struct Map6 {
+  PrunedArgs s;                          // the search, and its replay for an overflowed wave in the placing pass
+  HitList hl;
+  int search_blocks, hit_waves;          // blocks of the search; its waves = regions of the hit list
+  int place_blocks;                      // the placing pass: that many blocks stride over the regions
+  int RB;                                // 256-row blocks of the output map
+  uint32_t *mask_out, *mask_in;          // bit matrices [rows + 1][KW]; mask_in: maps with an in-major CSR, else NULL
+  unsigned short *wpre_out, *wpre_in;    // per-word prefixes of the rows' pair counts
+  int4 *cell;                            // transposed bit matrix (kmap_colmask)
+  int32_t *counts, *base;                // pairs per (offset, 256-row block) cell [K * RB] and their exclusive scan
+  int32_t *cnt_out;                      // pairs per output row -> km.out_ptr
+  DgrKernelMap km;                       // the lasting arrays (a copy of the caller's map once they are allocated)
+  // host side only
+  int32_t *total, *cnt_in;               // pairs of the map; pairs per input row -> km.in_ptr (with mask_in)
+  int64_t n_in_cap;
+};
+struct Maps6 {
+  Map6 m[KM_MAXJOBS];
+};
+static_assert(sizeof(Maps6) <= 4096, "the records of the 6-D builder travel as ONE by-value kernel argument (HIP: 4 KB)");
+
 // The searches of ALL maps of a sparse tensor in one launch (round 5; round 4 launched map after map: seven grids of
 // 38-250 us each with their tails idle): blockIdx.y = map, blockIdx.x = the map's search block (surplus blocks of the
 // smaller maps exit at once).
-struct Bits6Jobs {
-  PrunedArgs pa[KM_JOBS6];
-  uint32_t *mask_out[KM_JOBS6], *mask_in[KM_JOBS6];
-  HitList hl[KM_JOBS6];
-  int blocks[KM_JOBS6];
-};
 __global__ void __launch_bounds__(KM_THREADS)
-    kmap_bits_pruned6(Bits6Jobs J, int KW) {
+    kmap_bits_pruned6(Maps6 J, int KW) {
   __shared__ int hit_cur[KM_THREADS / 64];
-  const int jm = blockIdx.y;
-  if ((int)blockIdx.x >= J.blocks[jm]) return;
-  const PrunedArgs a = J.pa[jm];
-  uint32_t *const mask_out = J.mask_out[jm], *const mask_in = J.mask_in[jm];
-  const HitList hl = J.hl[jm];
+  const Map6 &M = J.m[blockIdx.y];
+  if ((int)blockIdx.x >= M.search_blocks) return;
+  const PrunedArgs &a = M.s;
+  uint32_t *const mask_out = M.mask_out, *const mask_in = M.mask_in;
+  const HitList &hl = M.hl;
   hit_begin(hit_cur);
   const int wid = (int)(blockIdx.x * (KM_THREADS / 64) + (threadIdx.x >> 6));
   // (no early return: every wave leaves its record count behind)
@@ -299,25 +316,17 @@ __global__ void __launch_bounds__(KM_THREADS)
 // (offset, 256-row block) cell.  A pair's position = cell base (exclusive scan of counts) + the pairs of the earlier
 // groups of the same block (here) + its rank inside the group's ballot (place_pair).
 constexpr int KM_KMAX = 736;
-struct Colmask6Jobs {   // blockIdx.y = map, blockIdx.x = 256-row block of the map
-  const uint32_t *mask_out[KM_JOBS6];
-  const int32_t *n_out_dev[KM_JOBS6];
-  int RB[KM_JOBS6];
-  int4 *cell[KM_JOBS6];
-  int32_t *counts[KM_JOBS6], *row_cnt[KM_JOBS6];
-  unsigned short *wpre[KM_JOBS6];
-};
 __global__ void __launch_bounds__(KM_THREADS)
-    kmap_colmask(Colmask6Jobs J, int K, int KW) {
+    kmap_colmask(Maps6 J, int K, int KW) {   // blockIdx.y = map, blockIdx.x = 256-row block of the map
   __shared__ unsigned long long bal[KM_THREADS / 64][KM_KMAX];
-  const int jm = blockIdx.y;
-  const int RB = J.RB[jm];
+  const Map6 &M = J.m[blockIdx.y];
+  const int RB = M.RB;
   if ((int)blockIdx.x >= RB) return;
-  const uint32_t *__restrict__ mask_out = J.mask_out[jm];
-  const int32_t *n_out_dev = J.n_out_dev[jm];
-  int4 *__restrict__ cell = J.cell[jm];
-  int32_t *__restrict__ counts = J.counts[jm], *__restrict__ row_cnt = J.row_cnt[jm];
-  unsigned short *__restrict__ wpre = J.wpre[jm];
+  const uint32_t *__restrict__ mask_out = M.mask_out;
+  const int32_t *n_out_dev = M.s.n_out_dev;
+  int4 *__restrict__ cell = M.cell;
+  int32_t *__restrict__ counts = M.counts, *__restrict__ row_cnt = M.cnt_out;
+  unsigned short *__restrict__ wpre = M.wpre_out;
   const int rb = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n_out = *n_out_dev;
@@ -358,71 +367,49 @@ __global__ void __launch_bounds__(KM_THREADS)
   }
 }
 
-// everything needed to put ONE pair (k, o) -> in into the map.  pair_out / pair_k may be NULL (maps whose consumers
-// never read them): two random stores less per pair.
-struct PlaceArgs {
-  int K, KW, RB;
-  const uint32_t *mask_out;
-  const int32_t *out_ptr;
-  const int4 *cell;
-  const int32_t *base;
-  int32_t *pair_in, *pair_out;
-  uint16_t *pair_k;
-  int32_t *out_pos;
-  int64_t pair_cap;
-  int32_t *overflow;
-  const uint32_t *mask_in;
-  const int32_t *in_ptr;
-  int32_t *in_pos;
-  const unsigned short *wpre_out, *wpre_in;
-};
-__device__ __forceinline__ void place_pair(const PlaceArgs &p, int k, int64_t o, int64_t in) {
-  const int64_t slot = (int64_t)p.out_ptr[o] + mask_rank_pre(p.mask_out + o * p.KW, p.wpre_out + o * p.KW, k);
+// puts ONE pair (k, o) -> in into map p.  km.pair_out / km.pair_k may be NULL (maps whose consumers never read them):
+// two random stores less per pair.
+__device__ __forceinline__ void place_pair(const Map6 &p, int K, int KW, int32_t *overflow, int k, int64_t o, int64_t in) {
+  const int64_t slot = (int64_t)p.km.out_ptr[o] + mask_rank_pre(p.mask_out + o * KW, p.wpre_out + o * KW, k);
   const int64_t g = o >> 6;
-  const int4 c = p.cell[g * p.K + k];   // ONE 16-byte read: column ballot + pairs of the block's earlier groups
+  const int4 c = p.cell[g * K + k];   // ONE 16-byte read: column ballot + pairs of the block's earlier groups
   const unsigned long long cm = ((unsigned long long)(uint32_t)c.y << 32) | (uint32_t)c.x;
   const int64_t pos = (int64_t)p.base[(int64_t)k * p.RB + (g >> 2)] + c.z + __popcll(cm & ((1ull << (o & 63)) - 1ull));
-  if (pos < p.pair_cap && slot < p.pair_cap) {
-    p.pair_in[pos] = (int32_t)in;
-    if (p.pair_out) p.pair_out[pos] = (int32_t)o;
-    if (p.pair_k) p.pair_k[pos] = (uint16_t)k;
-    p.out_pos[slot] = (int32_t)pos;
-    if (p.mask_in) p.in_pos[p.in_ptr[in] + mask_rank_pre(p.mask_in + in * p.KW, p.wpre_in + in * p.KW, k)] = (int32_t)pos;
+  if (pos < p.km.pair_cap && slot < p.km.pair_cap) {
+    p.km.pair_in[pos] = (int32_t)in;
+    if (p.km.pair_out) p.km.pair_out[pos] = (int32_t)o;
+    if (p.km.pair_k) p.km.pair_k[pos] = (uint16_t)k;
+    p.km.out_pos[slot] = (int32_t)pos;
+    if (p.mask_in) p.km.in_pos[p.km.in_ptr[in] + mask_rank_pre(p.mask_in + in * KW, p.wpre_in + in * KW, k)] = (int32_t)pos;
   } else {
-    *p.overflow = 2;
+    *overflow = 2;
   }
 }
 
 // one wave per region of the hit list: one lane per record places the pair; a wave whose region overflowed during the
-// search (count -1) repeats that wave's search and places what it finds
-struct Place6Jobs {   // blockIdx.y = map; the map's blocks stride over its hit-list regions
-  HitList h[KM_JOBS6];
-  PlaceArgs p[KM_JOBS6];
-  PrunedArgs replay[KM_JOBS6];
-  int n_waves[KM_JOBS6], blocks[KM_JOBS6];
-};
+// search (count -1) repeats that wave's search and places what it finds.  blockIdx.y = map; the map's blocks stride
+// over its hit-list regions.
 __global__ void __launch_bounds__(KM_THREADS)
-    kmap_place_hits(Place6Jobs J) {
-  const int jm = blockIdx.y;
-  const int nblk = J.blocks[jm];
+    kmap_place_hits(Maps6 J, int K, int KW, int32_t *overflow) {
+  const Map6 &p = J.m[blockIdx.y];
+  const int nblk = p.place_blocks;
   if ((int)blockIdx.x >= nblk) return;
-  const HitList h = J.h[jm];
-  const PlaceArgs p = J.p[jm];
-  const PrunedArgs replay = J.replay[jm];
-  const int n_waves = J.n_waves[jm];
+  const HitList &h = p.hl;
+  const PrunedArgs &replay = p.s;
+  const int n_waves = p.hit_waves;
   const int lane = threadIdx.x & 63;
   for (int r = blockIdx.x * (KM_THREADS / 64) + (threadIdx.x >> 6); r < n_waves; r += nblk * (KM_THREADS / 64)) {
     const int n = h.wave_count[r];
     if (n < 0) {
       pruned_search6(replay, (int64_t)r * 64 + lane, [&](int k, int64_t o, int in) {
-        place_pair(p, k, o, in);
-        if (replay.symmetric && 728 - k != k) place_pair(p, 728 - k, in, o);
+        place_pair(p, K, KW, overflow, k, o, in);
+        if (replay.symmetric && 728 - k != k) place_pair(p, K, KW, overflow, 728 - k, in, o);
       });
       continue;
     }
     for (int e = lane; e < n; e += 64) {
       const unsigned long long rec = h.recs[(int64_t)r * h.region + e];
-      place_pair(p, (int)(rec >> 54), (int64_t)((rec >> 27) & 0x7ffffffull), (int64_t)(rec & 0x7ffffffull));
+      place_pair(p, K, KW, overflow, (int)(rec >> 54), (int64_t)((rec >> 27) & 0x7ffffffull), (int64_t)(rec & 0x7ffffffull));
     }
   }
 }
@@ -478,7 +465,6 @@ __global__ void __launch_bounds__(KM_THREADS)
 
 // Finalisation of up to KM_MAXJOBS kernel maps in ONE launch each (blockIdx.x / blockIdx.y = map): the seven 6-D maps of
 // a forward reach this point together (build_kernel_maps6).
-constexpr int KM_MAXJOBS = 8;
 struct FinalizeJobs {
   const int32_t *base[KM_MAXJOBS], *total[KM_MAXJOBS];
   int32_t *rule_ptr[KM_MAXJOBS], *tile_ptr[KM_MAXJOBS];
@@ -532,9 +518,25 @@ __global__ void tile_desc_kernel(FinalizeJobs j) {
   tile_desc_one(j.tile_ptr[m], j.rule_ptr[m], j.K[m], j.desc[m], j.tile_cap[m], t, DGR_TILE_M);
 }
 
+// What a map keeps besides pair_in and the out-major CSR.  `lean` (the network forward): pair_out is only read by the
+// transposed convs (strided maps used swapped, which also need the in-major CSR), pair_k only by the small-Cin conv1
+// (same[0] / the conv1 map); the stand-alone maps object keeps everything.  The same for D = 3 and D = 6.
+struct MapKeep {
+  bool in_csr, pair_out, pair_k;
+};
+enum MapRole { MAP_SAME, MAP_CONV1, MAP_DOWN, MAP_LIST };   // same[level], conv1 (ks != 3), down[level], a list made from a table
+static MapKeep map_keep(const DgrMapsMode &mode, MapRole role, int level) {
+  switch (role) {
+    case MAP_SAME: return {false, !mode.lean, !mode.lean || level == 0};
+    case MAP_CONV1: return {false, !mode.lean, true};
+    case MAP_DOWN: return {true, true, !mode.lean};
+    default: return {false, false, false};
+  }
+}
+
 // the parts of a kernel map that outlive the build
-static int alloc_kernel_map(DgrArena &arena, int K, int64_t n_cap, int64_t n_in_cap, int max_pairs_per_row, bool need_in_csr,
-                            bool want_pair_out, bool want_pair_k, DgrKernelMap *km) {
+static int alloc_kernel_map(DgrArena &arena, int K, int64_t n_cap, int64_t n_in_cap, int max_pairs_per_row, MapKeep keep,
+                            DgrKernelMap *km) {
   DGR_REQUIRE(K <= 1024, "kernel volume %d > 1024 not supported", K);
   km->K = K;
   const int64_t per_row = K < max_pairs_per_row ? K : max_pairs_per_row;
@@ -544,35 +546,68 @@ static int alloc_kernel_map(DgrArena &arena, int K, int64_t n_cap, int64_t n_in_
   DGR_ALLOC(km->tile_ptr, arena, int32_t, K + 1);
   DGR_ALLOC(km->pair_in, arena, int32_t, km->pair_cap);
   km->pair_out = nullptr;
-  if (want_pair_out) DGR_ALLOC(km->pair_out, arena, int32_t, km->pair_cap);
+  if (keep.pair_out) DGR_ALLOC(km->pair_out, arena, int32_t, km->pair_cap);
   km->tile_cap = km->pair_cap / DGR_TILE_M + K;
   DGR_ALLOC(km->tile_desc, arena, int4, km->tile_cap);
   DGR_ALLOC(km->out_ptr, arena, int32_t, n_cap + 1);
   DGR_ALLOC(km->out_pos, arena, int32_t, km->pair_cap);
   km->pair_k = nullptr;
-  if (want_pair_k) DGR_ALLOC(km->pair_k, arena, uint16_t, km->pair_cap);
-  if (need_in_csr) {
+  if (keep.pair_k) DGR_ALLOC(km->pair_k, arena, uint16_t, km->pair_cap);
+  km->in_ptr = km->in_pos = nullptr;
+  if (keep.in_csr) {
     DGR_ALLOC(km->in_ptr, arena, int32_t, n_in_cap + 1);
     DGR_ALLOC(km->in_pos, arena, int32_t, km->pair_cap);
   }
   return DGR_OK;
 }
 
-static void finalize_job(FinalizeJobs &fj, int m, const int32_t *base, const int32_t *total, int K, int RB, DgrKernelMap *km) {
-  fj.base[m] = base; fj.total[m] = total; fj.K[m] = K; fj.RB[m] = RB;
-  fj.rule_ptr[m] = km->rule_ptr; fj.tile_ptr[m] = km->tile_ptr;
-  fj.desc[m] = km->tile_desc; fj.tile_cap[m] = km->tile_cap;
+// The closing pass of every builder, for all maps of a call together: ONE multi-array scan -- per map the row counts
+// -> km->out_ptr, the per-(offset, 256-row block) counts -> base and total, the input-row counts -> km->in_ptr where
+// the map has an in-major CSR --, one finalisation launch (rule_ptr, tile_ptr) and one tile-descriptor launch.
+struct MapClose {
+  const int32_t *counts;    // [km->K * RB]
+  int32_t *base, *total;
+  int RB;
+  const int32_t *cnt_out;   // [n_out]
+  int64_t n_out;
+  const int32_t *cnt_in;    // [n_in], or NULL
+  int64_t n_in;
+  DgrKernelMap *km;
+};
+static int close_maps(DgrArena &arena, const MapClose *maps, int nj, hipStream_t stream) {
+  DGR_REQUIRE(nj >= 1 && nj <= KM_MAXJOBS, "kernel maps: %d maps per closing pass", nj);
+  const int32_t *ins[DGR_SCAN_MAX];
+  int32_t *outs[DGR_SCAN_MAX], *tots[DGR_SCAN_MAX];
+  int64_t ns[DGR_SCAN_MAX];
+  int c = 0;
+  FinalizeJobs fj = {};
+  int64_t max_tiles = 0;
+  for (int m = 0; m < nj; ++m) {
+    const MapClose &M = maps[m];
+    const DgrKernelMap *km = M.km;
+    DGR_REQUIRE(c + (M.cnt_in ? 3 : 2) <= DGR_SCAN_MAX, "kernel maps: more than %d arrays to scan", DGR_SCAN_MAX);
+    ins[c] = M.cnt_out; outs[c] = km->out_ptr; tots[c] = nullptr; ns[c++] = M.n_out;
+    ins[c] = M.counts; outs[c] = M.base; tots[c] = M.total; ns[c++] = (int64_t)km->K * M.RB;
+    if (M.cnt_in) { ins[c] = M.cnt_in; outs[c] = km->in_ptr; tots[c] = nullptr; ns[c++] = M.n_in; }
+    fj.base[m] = M.base; fj.total[m] = M.total; fj.K[m] = km->K; fj.RB[m] = M.RB;
+    fj.rule_ptr[m] = km->rule_ptr; fj.tile_ptr[m] = km->tile_ptr;
+    fj.desc[m] = km->tile_desc; fj.tile_cap[m] = km->tile_cap;
+    max_tiles = std::max<int64_t>(max_tiles, km->tile_cap);
+  }
+  DGR_CHECK(dgr_exclusive_scan_multi(arena, c, ins, outs, ns, tots, stream));
+  kmap_finalize<<<nj, 1024, 0, stream>>>(fj);
+  tile_desc_kernel<<<dim3((unsigned)dgr_ceil_div(max_tiles, 256), (unsigned)nj), 256, 0, stream>>>(fj);
+  return DGR_OK;
 }
 
 // D = 3 (rule-major maps of 3-D nets that do not run on neighbour tables; the stand-alone maps object): one map per call
 static int build_kernel_map3(DgrArena &arena, const DgrCoordMap &in, const DgrCoordMap &out, int ks, int max_pairs_per_row,
-                             bool need_in_csr, bool want_pair_out, bool want_pair_k, DgrKernelMap *km,
-                             int32_t *overflow, hipStream_t stream) {
+                             MapKeep keep, DgrKernelMap *km, int32_t *overflow, hipStream_t stream) {
   constexpr int D = 3;
   const int K = ks * ks * ks;
   const int64_t n_cap = out.n_cap, n_in_cap = in.n_cap;
   const int RB = (int)dgr_ceil_div(n_cap, KM_THREADS);
-  DGR_CHECK(alloc_kernel_map(arena, K, n_cap, n_in_cap, max_pairs_per_row, need_in_csr, want_pair_out, want_pair_k, km));
+  DGR_CHECK(alloc_kernel_map(arena, K, n_cap, n_in_cap, max_pairs_per_row, keep, km));
   const int KW = (K + 31) / 32;
   // transients (released after the last pass): per-(offset, block) counts, row bitmasks and the dense hit cache [K, n_cap]
   DgrArena::Mark mk = arena.mark();
@@ -583,13 +618,13 @@ static int build_kernel_map3(DgrArena &arena, const DgrCoordMap &in, const DgrCo
   uint32_t *mask_out, *mask_in = nullptr;
   int32_t *cnt_out, *cnt_in = nullptr;
   {
-    const size_t w_out = (size_t)(n_cap + 1) * KW, w_in = need_in_csr ? (size_t)(n_in_cap + 1) * KW : 0;
+    const size_t w_out = (size_t)(n_cap + 1) * KW, w_in = keep.in_csr ? (size_t)(n_in_cap + 1) * KW : 0;
     DGR_ALLOC(mask_out, arena, uint32_t, w_out + w_in);
-    if (need_in_csr) mask_in = mask_out + w_out;
+    if (keep.in_csr) mask_in = mask_out + w_out;
     DGR_HIP_CHECK(hipMemsetAsync(mask_out, 0, (w_out + w_in) * sizeof(uint32_t), stream));
   }
   DGR_ALLOC(cnt_out, arena, int32_t, n_cap + 1);
-  if (need_in_csr) DGR_ALLOC(cnt_in, arena, int32_t, n_in_cap + 1);
+  if (keep.in_csr) DGR_ALLOC(cnt_in, arena, int32_t, n_in_cap + 1);
   int32_t *hits;
   DGR_ALLOC(hits, arena, int32_t, (int64_t)K * n_cap);
   kmap_search<D><<<dim3(RB, K), KM_THREADS, 0, stream>>>(out.coords, out.n_dev, in.coords, in.table, in.table_mask, ks,
@@ -597,18 +632,10 @@ static int build_kernel_map3(DgrArena &arena, const DgrCoordMap &in, const DgrCo
   DGR_LAUNCH_CHECK();
   // per-row pair counts -> CSR row pointers (out rows; in rows for maps used swapped)
   mask_count_kernel<<<(int)dgr_ceil_div(n_cap + 1, 256), 256, 0, stream>>>(mask_out, KW, out.n_dev, n_cap + 1, cnt_out);
-  if (need_in_csr)
+  if (keep.in_csr)
     mask_count_kernel<<<(int)dgr_ceil_div(n_in_cap + 1, 256), 256, 0, stream>>>(mask_in, KW, in.n_dev, n_in_cap + 1, cnt_in);
-  {
-    const int32_t *ins[3] = {cnt_out, counts, cnt_in};
-    int32_t *outs[3] = {km->out_ptr, base, km->in_ptr}, *tots[3] = {nullptr, total, nullptr};
-    const int64_t ns[3] = {n_cap + 1, (int64_t)K * RB, n_in_cap + 1};
-    DGR_CHECK(dgr_exclusive_scan_multi(arena, need_in_csr ? 3 : 2, ins, outs, ns, tots, stream));
-  }
-  FinalizeJobs fj = {};
-  finalize_job(fj, 0, base, total, K, RB, km);
-  kmap_finalize<<<1, 1024, 0, stream>>>(fj);
-  tile_desc_kernel<<<dim3((unsigned)dgr_ceil_div(km->tile_cap, 256), 1), 256, 0, stream>>>(fj);
+  const MapClose mc = {counts, base, total, RB, cnt_out, n_cap + 1, cnt_in, n_in_cap + 1, km};
+  DGR_CHECK(close_maps(arena, &mc, 1, stream));
   kmap_fill<<<dim3(RB, (K + KM_KGROUP - 1) / KM_KGROUP), KM_THREADS, 0, stream>>>(
       out.n_dev, RB, K, n_cap, hits, counts, base, km->pair_in, km->pair_out, km->pair_cap, overflow, KW, mask_out,
       km->out_ptr, km->out_pos, mask_in, km->in_ptr, km->in_pos, km->pair_k);
@@ -627,149 +654,94 @@ struct Kmap6Job {
   const DgrCoordMap *in, *out;
   const DgrHalfBuckets *hb;     // first-half buckets of `in`
   const DgrHalfBuckets *hb_out; // ... of `out` (the order the search walks the output rows in)
-  bool need_in_csr, want_pair_out, want_pair_k;
+  MapKeep keep;
   DgrKernelMap *km;
 };
 static int build_kernel_maps6(DgrArena &arena, const Kmap6Job *jobs, int nj, int max_pairs_per_row, int32_t *overflow,
                               hipStream_t stream) {
   constexpr int K = 729, KW = (K + 31) / 32;
   DGR_REQUIRE(nj >= 1 && nj <= KM_MAXJOBS, "6-D kernel maps: %d jobs", nj);
-  struct Tr {   // transients of one job
-    int RB, symmetric;
-    int64_t n_cap, n_in_cap, hit_waves;
-    int32_t *counts, *base, *total, *cnt_out, *cnt_in;
-    uint32_t *mask_out, *mask_in;
-    int4 *cell;
-    HitList hl;
-    unsigned short *wpre_out, *wpre_in;
-  } t[KM_MAXJOBS];
+  Maps6 R = {};
+  int max_sb = 0, max_rb = 0, max_pb = 0;
   for (int m = 0; m < nj; ++m) {
     const Kmap6Job &J = jobs[m];
-    t[m].n_cap = J.out->n_cap; t[m].n_in_cap = J.in->n_cap;
-    DGR_REQUIRE(t[m].n_cap < (1ll << 27) && t[m].n_in_cap < (1ll << 27), "6-D kernel maps: more than 2^27 rows");
-    DGR_CHECK(alloc_kernel_map(arena, K, t[m].n_cap, t[m].n_in_cap, max_pairs_per_row, J.need_in_csr, J.want_pair_out,
-                               J.want_pair_k, J.km));
+    Map6 &r = R.m[m];
+    DGR_REQUIRE(J.hb && J.hb->built && J.hb_out && J.hb_out->built, "6-D kernel map: first-half buckets missing");
+    const int64_t n_cap = J.out->n_cap;
+    r.n_in_cap = J.in->n_cap;
+    DGR_REQUIRE(n_cap < (1ll << 27) && r.n_in_cap < (1ll << 27), "6-D kernel maps: more than 2^27 rows");
+    DGR_CHECK(alloc_kernel_map(arena, K, n_cap, r.n_in_cap, max_pairs_per_row, J.keep, J.km));
+    r.km = *J.km;
+    r.RB = (int)dgr_ceil_div(n_cap, KM_THREADS);
+    // same-stride maps (in and out are the SAME coordinate set) are symmetric: search half the offsets
+    const int symmetric = (J.in->coords == J.out->coords && !J.keep.in_csr) ? 1 : 0;
+    r.s = PrunedArgs{J.out->coords, J.out->n_dev, J.hb_out->second, n_cap, *J.hb, J.in->ts, symmetric};
+    // hit list: one region per wave of the search (thread = (first-half offset, row in bucket order)); a wave whose
+    // region overflows is replayed by the placing kernel
+    const int64_t search_blocks = dgr_ceil_div(n_cap * (symmetric ? 14 : 27), KM_THREADS);
+    DGR_REQUIRE(search_blocks * (KM_THREADS / 64) < (1ll << 31), "6-D kernel map: too many search waves");
+    r.search_blocks = (int)search_blocks;
+    r.hit_waves = r.search_blocks * (KM_THREADS / 64);
+    r.place_blocks = std::min(r.search_blocks, 16384);
+    r.hl.region = km_region_of(J.in->ts, symmetric);
+    max_sb = std::max(max_sb, r.search_blocks);
+    max_rb = std::max(max_rb, r.RB);
+    max_pb = std::max(max_pb, r.place_blocks);
   }
   DgrArena::Mark mk = arena.mark();
-  // the bit matrices (out rows; in rows for maps used swapped) and the row counts of ALL jobs: one allocation, one clear
+  // the bit matrices (out rows; in rows for maps used swapped) and the row counts of ALL maps: one allocation, one clear
+  // (kmap_colmask leaves cnt_out of the rows beyond the count to this clear)
   {
     size_t words = 0;
     for (int m = 0; m < nj; ++m)
-      words += (size_t)(t[m].n_cap + 1) * KW + (jobs[m].need_in_csr ? (size_t)(t[m].n_in_cap + 1) * KW : 0) + (size_t)(t[m].n_cap + 1);
+      words += (size_t)(R.m[m].s.n_cap + 1) * (KW + 1) + (jobs[m].keep.in_csr ? (size_t)(R.m[m].n_in_cap + 1) * KW : 0);
     uint32_t *pool;
     DGR_ALLOC(pool, arena, uint32_t, words);
     DGR_HIP_CHECK(hipMemsetAsync(pool, 0, words * sizeof(uint32_t), stream));
     for (int m = 0; m < nj; ++m) {
-      t[m].mask_out = pool; pool += (size_t)(t[m].n_cap + 1) * KW;
-      t[m].mask_in = nullptr;
-      if (jobs[m].need_in_csr) { t[m].mask_in = pool; pool += (size_t)(t[m].n_in_cap + 1) * KW; }
-      t[m].cnt_out = reinterpret_cast<int32_t *>(pool); pool += (size_t)(t[m].n_cap + 1);
+      Map6 &r = R.m[m];
+      r.mask_out = pool; pool += (size_t)(r.s.n_cap + 1) * KW;
+      if (jobs[m].keep.in_csr) { r.mask_in = pool; pool += (size_t)(r.n_in_cap + 1) * KW; }
+      r.cnt_out = reinterpret_cast<int32_t *>(pool); pool += (size_t)(r.s.n_cap + 1);
     }
   }
+  MapClose mc[KM_MAXJOBS];
+  MaskCountJobs mj = {};   // the input rows of the maps with an in-major CSR
+  int nm = 0;
+  long long max_rows = 0;
   for (int m = 0; m < nj; ++m) {
-    const Kmap6Job &J = jobs[m];
-    Tr &r = t[m];
-    r.RB = (int)dgr_ceil_div(r.n_cap, KM_THREADS);
-    // same-stride maps (in and out are the SAME coordinate set) are symmetric: search half the offsets
-    r.symmetric = (J.in->coords == J.out->coords && !J.need_in_csr) ? 1 : 0;
-    DGR_REQUIRE(J.hb && J.hb->built && J.hb_out && J.hb_out->built, "6-D kernel map: first-half buckets missing");
+    Map6 &r = R.m[m];
+    const int64_t n_cap = r.s.n_cap;
+    const bool in_csr = jobs[m].keep.in_csr;
     DGR_ALLOC(r.counts, arena, int32_t, (int64_t)K * r.RB);
     DGR_ALLOC(r.base, arena, int32_t, (int64_t)K * r.RB);
     DGR_ALLOC(r.total, arena, int32_t, 1);
-    r.cnt_in = nullptr;
-    if (J.need_in_csr) DGR_ALLOC(r.cnt_in, arena, int32_t, r.n_in_cap + 1);
+    if (in_csr) DGR_ALLOC(r.cnt_in, arena, int32_t, r.n_in_cap + 1);
     DGR_ALLOC(r.cell, arena, int4, (int64_t)r.RB * (KM_THREADS / 64) * K);
-    // hit list: one region per wave of the search (thread = (first-half offset, row in bucket order)); a wave whose
-    // region overflows is replayed by the placing kernel
-    const int64_t search_blocks = dgr_ceil_div(r.n_cap * (r.symmetric ? 14 : 27), KM_THREADS);
-    r.hit_waves = search_blocks * (KM_THREADS / 64);
-    // (a wave = 64 rows under one first-half offset: a dozen records at the fine levels and in the strided maps, ~180 in
-    // the stride-8 map with its 39 neighbours per row, several times that in its dense corners)
-    r.hl.region = (J.in->ts >= 8 && r.symmetric) ? 2 * KM_REGION : KM_REGION / 2;
-    DGR_REQUIRE(r.hit_waves < (1ll << 31), "6-D kernel map: too many search waves");
-    DGR_ALLOC(r.hl.recs, arena, unsigned long long, r.hit_waves * r.hl.region);
+    DGR_ALLOC(r.hl.recs, arena, unsigned long long, (int64_t)r.hit_waves * r.hl.region);
     DGR_ALLOC(r.hl.wave_count, arena, int32_t, r.hit_waves);
-    DGR_ALLOC(r.wpre_out, arena, unsigned short, (r.n_cap + 1) * KW);
-    r.wpre_in = nullptr;
-    if (J.need_in_csr) DGR_ALLOC(r.wpre_in, arena, unsigned short, (r.n_in_cap + 1) * KW);
-  }
-  // ---- search (bits + hit records) of all maps in one launch, then the transposing / counting passes in one launch
-  static_assert(KM_JOBS6 >= KM_MAXJOBS, "multi-job launch tables");
-  {
-    Bits6Jobs bj = {};
-    Colmask6Jobs cj = {};
-    int max_sb = 0, max_rb = 0;
-    for (int m = 0; m < nj; ++m) {
-      const Kmap6Job &J = jobs[m];
-      Tr &r = t[m];
-      bj.pa[m] = PrunedArgs{J.out->coords, J.out->n_dev, J.hb_out->second, r.n_cap, *J.hb, J.in->ts, r.symmetric};
-      bj.mask_out[m] = r.mask_out; bj.mask_in[m] = r.mask_in; bj.hl[m] = r.hl;
-      bj.blocks[m] = (int)(r.hit_waves / (KM_THREADS / 64));
-      max_sb = std::max(max_sb, bj.blocks[m]);
-      cj.mask_out[m] = r.mask_out; cj.n_out_dev[m] = J.out->n_dev; cj.RB[m] = r.RB; cj.cell[m] = r.cell;
-      cj.counts[m] = r.counts; cj.row_cnt[m] = r.cnt_out; cj.wpre[m] = r.wpre_out;
-      max_rb = std::max(max_rb, r.RB);
+    DGR_ALLOC(r.wpre_out, arena, unsigned short, (n_cap + 1) * KW);
+    if (in_csr) {
+      DGR_ALLOC(r.wpre_in, arena, unsigned short, (r.n_in_cap + 1) * KW);
+      mj.mask[nm] = r.mask_in; mj.n_dev[nm] = jobs[m].in->n_dev; mj.n_cap[nm] = r.n_in_cap + 1;
+      mj.cnt[nm] = r.cnt_in; mj.wpre[nm] = r.wpre_in;
+      max_rows = std::max(max_rows, mj.n_cap[nm]);
+      ++nm;
     }
-    kmap_bits_pruned6<<<dim3((unsigned)max_sb, (unsigned)nj), KM_THREADS, 0, stream>>>(bj, KW);
-    kmap_colmask<<<dim3((unsigned)max_rb, (unsigned)nj), KM_THREADS, 0, stream>>>(cj, K, KW);
-    {
-      MaskCountJobs mj = {};
-      int nm = 0;
-      long long max_rows = 0;
-      for (int m = 0; m < nj; ++m)
-        if (jobs[m].need_in_csr) {
-          mj.mask[nm] = t[m].mask_in; mj.n_dev[nm] = jobs[m].in->n_dev; mj.n_cap[nm] = t[m].n_in_cap + 1;
-          mj.cnt[nm] = t[m].cnt_in; mj.wpre[nm] = t[m].wpre_in;
-          max_rows = std::max(max_rows, mj.n_cap[nm]);
-          ++nm;
-        }
-      static_assert(KM_MC_JOBS >= KM_MAXJOBS, "mask-count job table");
-      if (nm) mask_count_multi<KW><<<dim3((unsigned)dgr_ceil_div(max_rows, 256), (unsigned)nm), 256, 0, stream>>>(mj);
-    }
+    mc[m] = MapClose{r.counts, r.base, r.total, r.RB, r.cnt_out, n_cap + 1, r.cnt_in, r.n_in_cap + 1, jobs[m].km};
   }
+  // ---- search (bits + hit records) of all maps in one launch, then the transposing / counting passes in one launch each
+  kmap_bits_pruned6<<<dim3((unsigned)max_sb, (unsigned)nj), KM_THREADS, 0, stream>>>(R, KW);
+  kmap_colmask<<<dim3((unsigned)max_rb, (unsigned)nj), KM_THREADS, 0, stream>>>(R, K, KW);
+  if (nm) mask_count_multi<KW><<<dim3((unsigned)dgr_ceil_div(max_rows, 256), (unsigned)nm), 256, 0, stream>>>(mj);
   DGR_LAUNCH_CHECK();
-  // ---- every scan of every map: CSR row pointers (out rows; in rows for maps used swapped) and the cell bases
-  {
-    const int32_t *ins[DGR_SCAN_MAX];
-    int32_t *outs[DGR_SCAN_MAX], *tots[DGR_SCAN_MAX];
-    int64_t ns[DGR_SCAN_MAX];
-    int c = 0;
-    for (int m = 0; m < nj; ++m) {
-      ins[c] = t[m].cnt_out; outs[c] = jobs[m].km->out_ptr; tots[c] = nullptr; ns[c++] = t[m].n_cap + 1;
-      ins[c] = t[m].counts; outs[c] = t[m].base; tots[c] = t[m].total; ns[c++] = (int64_t)K * t[m].RB;
-      if (jobs[m].need_in_csr) { ins[c] = t[m].cnt_in; outs[c] = jobs[m].km->in_ptr; tots[c] = nullptr; ns[c++] = t[m].n_in_cap + 1; }
-    }
-    DGR_CHECK(dgr_exclusive_scan_multi(arena, c, ins, outs, ns, tots, stream));
-  }
-  FinalizeJobs fj = {};
-  int64_t max_tiles = 0;
-  for (int m = 0; m < nj; ++m) {
-    finalize_job(fj, m, t[m].base, t[m].total, K, t[m].RB, jobs[m].km);
-    max_tiles = std::max<int64_t>(max_tiles, jobs[m].km->tile_cap);
-  }
-  kmap_finalize<<<nj, 1024, 0, stream>>>(fj);
-  tile_desc_kernel<<<dim3((unsigned)dgr_ceil_div(max_tiles, 256), nj), 256, 0, stream>>>(fj);
+  // ---- every scan of every map (CSR row pointers, cell bases), rule and tile pointers, tile descriptors
+  DGR_CHECK(close_maps(arena, mc, nj, stream));
   // ---- place: all maps in one launch
-  {
-    Place6Jobs pj = {};
-    int max_pb = 0;
-    for (int m = 0; m < nj; ++m) {
-      const Kmap6Job &J = jobs[m];
-      Tr &r = t[m];
-      DgrKernelMap *km = J.km;
-      pj.p[m] = PlaceArgs{K, KW, r.RB, r.mask_out, km->out_ptr, r.cell, r.base, km->pair_in, km->pair_out, km->pair_k, km->out_pos,
-                          km->pair_cap, overflow, r.mask_in, km->in_ptr, km->in_pos, r.wpre_out, r.wpre_in};
-      pj.replay[m] = PrunedArgs{J.out->coords, J.out->n_dev, J.hb_out->second, r.n_cap, *J.hb, J.in->ts, r.symmetric};
-      pj.h[m] = r.hl;
-      pj.n_waves[m] = (int)r.hit_waves;
-      pj.blocks[m] = (int)std::min<int64_t>(dgr_ceil_div(r.hit_waves, KM_THREADS / 64), 16384);
-      max_pb = std::max(max_pb, pj.blocks[m]);
-      km->built = true;
-    }
-    kmap_place_hits<<<dim3((unsigned)max_pb, (unsigned)nj), KM_THREADS, 0, stream>>>(pj);
-  }
+  kmap_place_hits<<<dim3((unsigned)max_pb, (unsigned)nj), KM_THREADS, 0, stream>>>(R, K, KW, overflow);
   DGR_LAUNCH_CHECK();
   arena.rewind(mk);
+  for (int m = 0; m < nj; ++m) jobs[m].km->built = true;
   return DGR_OK;
 }
 
@@ -1018,32 +990,18 @@ struct NbrListSpec {
   const DgrCoordMap *out;
   DgrKernelMap *km;
 };
-static int build_nbr_lists3(DgrArena &arena, const NbrListSpec *specs, int nj, hipStream_t stream) {
-  DGR_REQUIRE(nj >= 1 && nj <= NL_JOBS && 2 * nj <= DGR_SCAN_MAX, "neighbour-table lists: %d maps per call", nj);
+static int build_nbr_lists3(DgrArena &arena, const NbrListSpec *specs, int nj, MapKeep keep, hipStream_t stream) {
+  DGR_REQUIRE(nj >= 1 && nj <= NL_JOBS, "neighbour-table lists: %d maps per call", nj);
+  DGR_REQUIRE(!keep.in_csr && !keep.pair_out && !keep.pair_k, "neighbour-table lists: pair_in and the out-major CSR only");
   NbrListJobs J = {};
-  FinalizeJobs fj = {};
   for (int m = 0; m < nj; ++m) {
-    DgrKernelMap *km = specs[m].km;
     const int64_t n_cap = specs[m].out->n_cap;
     DGR_REQUIRE(specs[m].t->built && specs[m].t->n_pad >= n_cap, "neighbour-table lists: table %d is not built", m);
-    km->K = 27;
-    km->pair_cap = 27 * n_cap;
-    DGR_REQUIRE(km->pair_cap < (1ll << 31), "kernel map too large (%lld pairs)", (long long)km->pair_cap);
-    km->tile_cap = km->pair_cap / DGR_TILE_M + 27;
-    DGR_ALLOC(km->rule_ptr, arena, int32_t, 28);
-    DGR_ALLOC(km->tile_ptr, arena, int32_t, 28);
-    DGR_ALLOC(km->pair_in, arena, int32_t, km->pair_cap);
-    DGR_ALLOC(km->tile_desc, arena, int4, km->tile_cap);
-    DGR_ALLOC(km->out_ptr, arena, int32_t, n_cap + 1);
-    DGR_ALLOC(km->out_pos, arena, int32_t, km->pair_cap);
-    km->pair_out = nullptr; km->pair_k = nullptr; km->in_ptr = km->in_pos = nullptr;
+    DGR_CHECK(alloc_kernel_map(arena, 27, n_cap, 0, 27, keep, specs[m].km));   // at most one pair per (offset, row)
   }
   DgrArena::Mark mk = arena.mark();
-  const int32_t *ins[2 * NL_JOBS];
-  int32_t *outs[2 * NL_JOBS], *tots[2 * NL_JOBS];
-  int64_t ns[2 * NL_JOBS];
+  MapClose mc[NL_JOBS];
   int max_rb = 0;
-  long long max_tiles = 0;
   for (int m = 0; m < nj; ++m) {
     DgrKernelMap *km = specs[m].km;
     const int64_t n_cap = specs[m].out->n_cap;
@@ -1056,17 +1014,12 @@ static int build_nbr_lists3(DgrArena &arena, const NbrListSpec *specs, int nj, h
     J.nbr[m] = specs[m].t->nbr; J.n_out_dev[m] = specs[m].out->n_dev; J.n_pad[m] = specs[m].t->n_pad; J.n_cap[m] = n_cap;
     J.RB[m] = RB; J.counts[m] = counts; J.cnt_out[m] = cnt_out; J.base[m] = base; J.out_ptr[m] = km->out_ptr;
     J.pair_in[m] = km->pair_in; J.out_pos[m] = km->out_pos;
-    ins[2 * m] = cnt_out; outs[2 * m] = km->out_ptr; tots[2 * m] = nullptr; ns[2 * m] = n_cap + 1;
-    ins[2 * m + 1] = counts; outs[2 * m + 1] = base; tots[2 * m + 1] = total; ns[2 * m + 1] = (int64_t)27 * RB;
-    finalize_job(fj, m, base, total, 27, RB, km);
+    mc[m] = MapClose{counts, base, total, RB, cnt_out, n_cap + 1, nullptr, 0, km};
     max_rb = std::max(max_rb, RB);
-    max_tiles = std::max<long long>(max_tiles, km->tile_cap);
   }
   nbr_list_count<<<dim3((unsigned)max_rb, (unsigned)nj), KM_THREADS, 0, stream>>>(J);
   DGR_LAUNCH_CHECK();
-  DGR_CHECK(dgr_exclusive_scan_multi(arena, 2 * nj, ins, outs, ns, tots, stream));
-  kmap_finalize<<<nj, 1024, 0, stream>>>(fj);
-  tile_desc_kernel<<<dim3((unsigned)dgr_ceil_div(max_tiles, 256), (unsigned)nj), 256, 0, stream>>>(fj);
+  DGR_CHECK(close_maps(arena, mc, nj, stream));
   nbr_list_fill<<<dim3((unsigned)max_rb, (unsigned)nj), KM_THREADS, 0, stream>>>(J);
   DGR_LAUNCH_CHECK();
   arena.rewind(mk);
@@ -1075,8 +1028,10 @@ static int build_nbr_lists3(DgrArena &arena, const NbrListSpec *specs, int nj, h
 }
 
 int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int conv1_ks,
-                   DgrMapSet *ms, hipStream_t stream, bool skip_conv1_map, bool lean, bool nbr_tables, bool nbr_lists) {
+                   DgrMapSet *ms, hipStream_t stream, DgrMapsMode mode) {
   DGR_REQUIRE(D == 3 || D == 6, "D=%d not supported (the DGR path uses D=3 and D=6)", D);
+  DGR_REQUIRE(!mode.tables || D == 3, "neighbour tables are a D = 3 structure");
+  DGR_REQUIRE(!mode.lists || (mode.lean && mode.tables), "lists from neighbour tables go with lean maps and D = 3");
   DGR_REQUIRE(conv1_ks % 2 == 1 && conv1_ks >= 1, "conv1 kernel size must be odd");
   DGR_REQUIRE(N > 0 && N < (1ll << 30), "N=%lld out of range", (long long)N);
   ms->D = D;
@@ -1087,9 +1042,8 @@ int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int
     DGR_HIP_CHECK(hipMemsetAsync(ms->overflow, 0, sizeof(int32_t), stream));
   }
   DGR_CHECK(dgr_build_coord_maps(arena, coords, N, ms, stream));
-  if (nbr_tables) {
+  if (mode.tables) {
     // D = 3 network forward: ten dense neighbour tables, ONE launch for all of them -- no pair lists, no CSR, no scans
-    DGR_REQUIRE(D == 3, "neighbour tables are a D = 3 structure");
     ms->use_nbr = true;
     NbrJobs nbj = {};
     int n_nbj = 0;
@@ -1115,327 +1069,40 @@ int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int
       cls_fill_kernel<<<dim3((unsigned)max_nb, 3), KM_THREADS, 0, stream>>>(cj);
       DGR_LAUNCH_CHECK();
     }
-    if (lean && nbr_lists) {
+    if (mode.lists) {
       // ... plus rule-major lists of the two coarse same-stride tables and the level 2 -> 3 strided one: the 128 / 256-channel
       // layers there run on the wide rule-major kernel (net.hip, layer_kind)
       const NbrListSpec specs[3] = {{&ms->nsame[2], &ms->cm[2], &ms->same[2]}, {&ms->nsame[3], &ms->cm[3], &ms->same[3]},
                                     {&ms->ndown[2], &ms->cm[3], &ms->down[2]}};
-      DGR_CHECK(build_nbr_lists3(arena, specs, 3, stream));
+      DGR_CHECK(build_nbr_lists3(arena, specs, 3, map_keep(mode, MAP_LIST, 0), stream));
     }
-    if (lean) {   // the network forward needs nothing else (conv1 runs fused with its neighbour search)
-      if (conv1_ks != 3 && !skip_conv1_map)
-        DGR_CHECK(build_kernel_map3(arena, ms->cm[0], ms->cm[0], conv1_ks, 1024, false, false, true, &ms->conv1, ms->overflow,
-                                    stream));
-      return DGR_OK;
-    }
+    // the network forward needs nothing else: conv1 runs fused with its neighbour search, whatever its kernel size
+    if (mode.lean) return DGR_OK;
   }
   // capacity per output row: exact (K) in 3-D; in 6-D 3^6 = 729 offsets but measured mean
   // occupancy is 2..40 neighbours -- reserve 160 per row and raise the overflow flag beyond.
   const int cap_row = (D == 3) ? 1024 : 160;
-  // `lean` (the network forward): pair_out is only read by the transposed convs (strided maps used swapped),
-  // pair_k only by the small-Cin conv1 (same[0] / the conv1 map); the stand-alone maps object keeps everything
   if (D == 6) {
     DGR_REQUIRE(conv1_ks == 3, "6-D kernel maps support kernel size 3 only (got %d)", conv1_ks);
     // first-half buckets of every level: the pruned search of all seven maps (since round 4 also at tensor stride 8)
     // (the coarse maps are numbered in bucket order on the way; level 0 keeps the caller's row order)
     DGR_CHECK(dgr_build_half_buckets(arena, ms->cm, ms->hb, 4, 1, stream));
     Kmap6Job jobs[7];
-    for (int l = 0; l < 4; ++l) jobs[l] = {&ms->cm[l], &ms->cm[l], &ms->hb[l], &ms->hb[l], false, !lean, !lean || l == 0, &ms->same[l]};
-    // strided maps are also used swapped by the transposed convs: the in-major CSR too
-    for (int l = 0; l < 3; ++l) jobs[4 + l] = {&ms->cm[l], &ms->cm[l + 1], &ms->hb[l], &ms->hb[l + 1], true, true, !lean, &ms->down[l]};
+    for (int l = 0; l < 4; ++l) jobs[l] = {&ms->cm[l], &ms->cm[l], &ms->hb[l], &ms->hb[l], map_keep(mode, MAP_SAME, l), &ms->same[l]};
+    for (int l = 0; l < 3; ++l)
+      jobs[4 + l] = {&ms->cm[l], &ms->cm[l + 1], &ms->hb[l], &ms->hb[l + 1], map_keep(mode, MAP_DOWN, l), &ms->down[l]};
     DGR_CHECK(build_kernel_maps6(arena, jobs, 7, cap_row, ms->overflow, stream));
     ms->conv1 = ms->same[0];
     return DGR_OK;
   }
-  auto build = [&](const DgrCoordMap &in, const DgrCoordMap &out, int ks, bool rev, bool want_k, DgrKernelMap *km) -> int {
-    const bool want_out = !lean || rev, want_pk = !lean || want_k;
-    return build_kernel_map3(arena, in, out, ks, cap_row, rev, want_out, want_pk, km, ms->overflow, stream);
+  auto build = [&](const DgrCoordMap &in, const DgrCoordMap &out, int ks, MapRole role, int l, DgrKernelMap *km) -> int {
+    return build_kernel_map3(arena, in, out, ks, cap_row, map_keep(mode, role, l), km, ms->overflow, stream);
   };
-  for (int l = 0; l < 4; ++l) DGR_CHECK(build(ms->cm[l], ms->cm[l], 3, false, l == 0, &ms->same[l]));
+  for (int l = 0; l < 4; ++l) DGR_CHECK(build(ms->cm[l], ms->cm[l], 3, MAP_SAME, l, &ms->same[l]));
   if (conv1_ks == 3)
     ms->conv1 = ms->same[0];
-  else if (!skip_conv1_map)
-    DGR_CHECK(build(ms->cm[0], ms->cm[0], conv1_ks, false, true, &ms->conv1));
-  // strided maps are also used swapped by the transposed convs: build the in-major CSR too
-  for (int l = 0; l < 3; ++l) DGR_CHECK(build(ms->cm[l], ms->cm[l + 1], 3, true, false, &ms->down[l]));
-  return DGR_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// stand-alone maps object (inspection / parity tests)
-// ------------------------------------------------------------------------------------------
-struct dgr_maps {
-  dgr_ctx *ctx;
-  DgrArena arena;  // private arena so the maps survive other calls on the ctx
-  DgrMapSet ms;
-  int32_t *coords_copy = nullptr;
-  hipStream_t stream;
-};
-
-static int maps_create(dgr_ctx *ctx, const int32_t *coords, int64_t N, int D, int conv1_kernel_size, int flags,
-                       dgr_maps **out, dgr_stream stream_) {
-  DGR_REQUIRE(ctx && coords && out, "dgr_maps_create: NULL argument");
-  DGR_REQUIRE((flags & ~(DGR_MAPS_LEAN | DGR_MAPS_NBR_LISTS)) == 0, "dgr_maps_create_ex: unknown flags 0x%x", flags);
-  DGR_REQUIRE(!(flags & DGR_MAPS_NBR_LISTS) || ((flags & DGR_MAPS_LEAN) && D == 3),
-              "dgr_maps_create_ex: DGR_MAPS_NBR_LISTS goes with DGR_MAPS_LEAN and D = 3");
-  // lean: the arguments of dgr_resunet_forward_impl (net.hip) -- a 3-D net runs on neighbour tables with conv1 fused
-  // with its search (no conv1 map), a 6-D net on lean rule-major maps
-  const bool lean = (flags & DGR_MAPS_LEAN) != 0;
-  const bool skip_conv1_map = lean && D == 3;
-  hipStream_t stream = (hipStream_t)stream_;
-  DGR_HIP_CHECK(hipSetDevice(ctx->device));
-  dgr_maps *m = new dgr_maps();
-  m->ctx = ctx;
-  m->stream = stream;
-  int rc = DGR_OK;
-  do {
-    m->coords_copy = m->arena.get<int32_t>((size_t)N * (D + 1));
-    if (!m->coords_copy) { rc = DGR_ENOMEM; break; }
-    if (hipMemcpyAsync(m->coords_copy, coords, (size_t)N * (D + 1) * sizeof(int32_t),
-                       hipMemcpyDeviceToDevice, stream) != hipSuccess) { rc = DGR_EHIP; break; }
-    rc = dgr_build_maps(m->arena, m->coords_copy, N, D, conv1_kernel_size, &m->ms, stream, skip_conv1_map, lean, D == 3,
-                        (flags & DGR_MAPS_NBR_LISTS) != 0);
-    if (rc != DGR_OK) break;
-    int32_t flag = 0;
-    if (hipMemcpyAsync(&flag, m->ms.overflow, sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess) { rc = DGR_EHIP; dgr_set_error("maps sync failed"); break; }
-    if (flag == 1) { dgr_set_error("duplicate coordinates in the sparse tensor input"); rc = DGR_EINVAL; break; }
-    if (flag == 2) { dgr_set_error("kernel-map capacity exceeded"); rc = DGR_ENOMEM; break; }
-  } while (0);
-  if (rc != DGR_OK) {
-    m->arena.release();
-    delete m;
-    return rc;
-  }
-  *out = m;
-  return DGR_OK;
-}
-
-extern "C" int dgr_maps_create(dgr_ctx *ctx, const int32_t *coords, int64_t N, int D,
-                               int conv1_kernel_size, dgr_maps **out, dgr_stream stream_) {
-  return maps_create(ctx, coords, N, D, conv1_kernel_size, 0, out, stream_);
-}
-
-extern "C" int dgr_maps_create_ex(dgr_ctx *ctx, const int32_t *coords, int64_t N, int D, int conv1_kernel_size,
-                                  int flags, dgr_maps **out, dgr_stream stream_) {
-  return maps_create(ctx, coords, N, D, conv1_kernel_size, flags, out, stream_);
-}
-
-extern "C" void dgr_maps_destroy(dgr_maps *m) {
-  if (!m) return;
-  (void)hipDeviceSynchronize();
-  m->arena.release();
-  delete m;
-}
-
-static int level_of(int ts) { return ts == 1 ? 0 : ts == 2 ? 1 : ts == 4 ? 2 : ts == 8 ? 3 : -1; }
-
-extern "C" int dgr_maps_get_coords(dgr_maps *m, int ts, int32_t *host_out, int64_t capacity,
-                                   int64_t *n) {
-  DGR_REQUIRE(m && n, "NULL argument");
-  int l = level_of(ts);
-  DGR_REQUIRE(l >= 0, "tensor stride %d not in {1,2,4,8}", ts);
-  int32_t n32 = 0;
-  DGR_HIP_CHECK(hipMemcpy(&n32, m->ms.cm[l].n_dev, sizeof(int32_t), hipMemcpyDeviceToHost));
-  *n = n32;
-  if (host_out) {
-    DGR_REQUIRE(capacity >= (int64_t)n32 * m->ms.nc, "host buffer too small");
-    const int nc = m->ms.nc;
-    if (!m->ms.cm[l].canon) {
-      DGR_HIP_CHECK(hipMemcpy(host_out, m->ms.cm[l].coords, (size_t)n32 * nc * sizeof(int32_t), hipMemcpyDeviceToHost));
-    } else {   // rows back in first-occurrence order
-      std::vector<int32_t> tmp((size_t)n32 * nc), canon(n32);
-      DGR_HIP_CHECK(hipMemcpy(tmp.data(), m->ms.cm[l].coords, tmp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-      DGR_HIP_CHECK(hipMemcpy(canon.data(), m->ms.cm[l].canon, canon.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-      for (int32_t p = 0; p < n32; ++p) memcpy(host_out + (size_t)canon[p] * nc, tmp.data() + (size_t)p * nc, nc * sizeof(int32_t));
-    }
-  }
-  return DGR_OK;
-}
-
-extern "C" int dgr_maps_get_kernel_map(dgr_maps *m, int kind, int ts, int32_t *rule_ptr,
-                                       int64_t rule_cap, int32_t *pair_in, int32_t *pair_out,
-                                       int64_t pair_cap, int64_t *K, int64_t *P) {
-  DGR_REQUIRE(m && K && P, "NULL argument");
-  int l = level_of(ts);
-  DGR_REQUIRE(l >= 0, "tensor stride %d not in {1,2,4,8}", ts);
-  if (kind >= 3 && kind <= 5) {
-    // D = 3 neighbour tables (kind 3: same stride, 4: ts -> 2 ts, 5: transposed 2 ts -> ts) as (k, in, out)
-    // triplets sorted by (k, out) -- the layout the rule-major getter returns
-    const DgrNbrTable *t = kind == 3 ? &m->ms.nsame[l] : (l < 3 ? (kind == 4 ? &m->ms.ndown[l] : &m->ms.nup[l]) : nullptr);
-    DGR_REQUIRE(t && t->built, "no such neighbour table (kind %d, ts %d)", kind, ts);
-    const DgrCoordMap &om = kind == 4 ? m->ms.cm[l + 1] : m->ms.cm[l];
-    int32_t n_out = 0;
-    DGR_HIP_CHECK(hipMemcpy(&n_out, om.n_dev, sizeof(int32_t), hipMemcpyDeviceToHost));
-    std::vector<int32_t> tab((size_t)t->n_pad * 27);
-    DGR_HIP_CHECK(hipMemcpy(tab.data(), t->nbr, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    *K = 27;
-    int64_t total = 0;
-    for (int k = 0; k < 27; ++k) {
-      if (rule_ptr && k < rule_cap) rule_ptr[k] = (int32_t)total;
-      for (int o = 0; o < n_out; ++o) {
-        const int32_t v = tab[(size_t)k * t->n_pad + o];
-        if (v < 0) continue;
-        if (pair_in && pair_out) {
-          DGR_REQUIRE(total < pair_cap, "pair buffers too small");
-          pair_in[total] = v;
-          pair_out[total] = o;
-        }
-        ++total;
-      }
-    }
-    if (rule_ptr) {
-      DGR_REQUIRE(rule_cap >= 28, "rule_ptr buffer too small");
-      rule_ptr[27] = (int32_t)total;
-    }
-    for (int64_t o = n_out; o < t->n_pad; ++o)
-      for (int k = 0; k < 27; ++k) DGR_REQUIRE(tab[(size_t)k * t->n_pad + o] == -1, "neighbour table padding is not -1");
-    *P = total;
-    return DGR_OK;
-  }
-  const DgrKernelMap *km = nullptr;
-  if (kind == 0) km = &m->ms.same[l];
-  else if (kind == 1) km = &m->ms.conv1;
-  else if (kind == 2 && l < 3) km = &m->ms.down[l];
-  DGR_REQUIRE(km && km->built, "no such kernel map (kind %d, ts %d)", kind, ts);
-  *K = km->K;
-  int32_t total = 0;
-  DGR_HIP_CHECK(hipMemcpy(&total, km->rule_ptr + km->K, sizeof(int32_t), hipMemcpyDeviceToHost));
-  *P = total;
-  if (rule_ptr) {
-    DGR_REQUIRE(rule_cap >= km->K + 1, "rule_ptr buffer too small");
-    DGR_HIP_CHECK(hipMemcpy(rule_ptr, km->rule_ptr, (size_t)(km->K + 1) * sizeof(int32_t),
-                            hipMemcpyDeviceToHost));
-  }
-  if (pair_in && pair_out) {
-    DGR_REQUIRE(pair_cap >= total, "pair buffers too small");
-    DGR_REQUIRE(km->pair_out, "this build kept no pair_out for the map (kind %d, ts %d): read it raw", kind, ts);
-    DGR_HIP_CHECK(hipMemcpy(pair_in, km->pair_in, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost));
-    DGR_HIP_CHECK(hipMemcpy(pair_out, km->pair_out, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost));
-    // rows in first-occurrence numbering (coarse 6-D maps are numbered by bucket inside the library), pairs of a rule
-    // sorted by output row in THAT numbering: the layout the getter documents
-    const DgrCoordMap &cin = m->ms.cm[l], &cout = m->ms.cm[kind == 2 ? l + 1 : l];
-    if (cin.canon || cout.canon) {
-      auto fetch = [&](const DgrCoordMap &c, std::vector<int32_t> &v) -> int {
-        if (!c.canon) return DGR_OK;
-        int32_t n = 0;
-        DGR_HIP_CHECK(hipMemcpy(&n, c.n_dev, sizeof(int32_t), hipMemcpyDeviceToHost));
-        v.resize(n);
-        DGR_HIP_CHECK(hipMemcpy(v.data(), c.canon, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        return DGR_OK;
-      };
-      std::vector<int32_t> ci, co, rp(km->K + 1);
-      DGR_CHECK(fetch(cin, ci));
-      DGR_CHECK(fetch(cout, co));
-      DGR_HIP_CHECK(hipMemcpy(rp.data(), km->rule_ptr, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-      std::vector<std::pair<int32_t, int32_t>> tmp;
-      for (int k = 0; k < km->K; ++k) {
-        tmp.clear();
-        for (int32_t q = rp[k]; q < rp[k + 1]; ++q)
-          tmp.push_back({cout.canon ? co[pair_out[q]] : pair_out[q], cin.canon ? ci[pair_in[q]] : pair_in[q]});
-        std::sort(tmp.begin(), tmp.end());
-        for (size_t u = 0; u < tmp.size(); ++u) { pair_out[rp[k] + u] = tmp[u].first; pair_in[rp[k] + u] = tmp[u].second; }
-      }
-    }
-  }
-  return DGR_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// raw read-back (test instrument): one array as it lies in memory, in the library's own numbering
-// ------------------------------------------------------------------------------------------
-extern "C" int dgr_maps_get_raw(dgr_maps *m, const char *kind, int ts, const char *field, void *host_out,
-                                int64_t capacity_bytes, int64_t *count, int64_t *elem_bytes) {
-  DGR_REQUIRE(m && kind && field && count && elem_bytes, "dgr_maps_get_raw: NULL argument");
-  const int l = level_of(ts);
-  DGR_REQUIRE(l >= 0, "tensor stride %d not in {1,2,4,8}", ts);
-  DGR_HIP_CHECK(hipSetDevice(m->ctx->device));
-  DGR_HIP_CHECK(hipStreamSynchronize(m->stream));
-  const DgrMapSet &ms = m->ms;
-  const auto is = [](const char *a, const char *b) { return strcmp(a, b) == 0; };
-  const void *dev = nullptr;   // device array to copy ...
-  int64_t n = 0, eb = 4;       // ... of n elements of eb bytes; or
-  bool scalar = false;         // one host value
-  int64_t value = 0;
-  const auto rows_of = [](const DgrCoordMap &c, int64_t *rows) -> int {
-    int32_t n32 = 0;
-    DGR_HIP_CHECK(hipMemcpy(&n32, c.n_dev, sizeof(int32_t), hipMemcpyDeviceToHost));
-    *rows = n32;
-    return DGR_OK;
-  };
-  if (is(kind, "level")) {
-    const DgrCoordMap &c = ms.cm[l];
-    int64_t rows = 0;
-    DGR_CHECK(rows_of(c, &rows));
-    if (is(field, "coords")) { dev = c.coords; n = rows * ms.nc; }
-    else if (is(field, "canon")) {
-      DGR_REQUIRE(c.canon, "level ts %d is not renumbered: it has no canon", ts);
-      dev = c.canon; n = rows;
-    }
-    else if (is(field, "table")) { dev = c.table; n = (int64_t)c.table_mask + 1; }
-    else if (is(field, "n")) { scalar = true; value = rows; }
-    else if (is(field, "mask")) { scalar = true; value = c.table_mask; }
-    else DGR_REQUIRE(false, "no field '%s' in a level", field);
-  } else if (is(kind, "same") || is(kind, "conv1") || is(kind, "down")) {
-    const bool down = is(kind, "down");
-    DGR_REQUIRE(!down || l < 3, "no strided map at ts %d", ts);
-    DGR_REQUIRE(!is(kind, "conv1") || l == 0, "the conv1 map lives at ts 1");
-    const DgrKernelMap *km = down ? &ms.down[l] : is(kind, "conv1") ? &ms.conv1 : &ms.same[l];
-    DGR_REQUIRE(km->built, "this build made no '%s' map at ts %d", kind, ts);
-    const DgrCoordMap &cin = ms.cm[l], &cout = ms.cm[down ? l + 1 : l];
-    int32_t tot[2] = {0, 0};   // pairs, tiles
-    DGR_HIP_CHECK(hipMemcpy(&tot[0], km->rule_ptr + km->K, sizeof(int32_t), hipMemcpyDeviceToHost));
-    DGR_HIP_CHECK(hipMemcpy(&tot[1], km->tile_ptr + km->K, sizeof(int32_t), hipMemcpyDeviceToHost));
-    const int64_t P = std::min<int64_t>(std::max<int64_t>(tot[0], 0), km->pair_cap);
-    const int64_t T = std::min<int64_t>(std::max<int64_t>(tot[1], 0), km->tile_cap);
-    if (is(field, "rule_ptr")) { dev = km->rule_ptr; n = km->K + 1; }
-    else if (is(field, "tile_ptr")) { dev = km->tile_ptr; n = km->K + 1; }
-    else if (is(field, "tile_desc")) { dev = km->tile_desc; n = 4 * T; }
-    else if (is(field, "pair_in")) { dev = km->pair_in; n = P; }
-    else if (is(field, "pair_out")) {
-      DGR_REQUIRE(km->pair_out, "this build kept no pair_out for the '%s' map at ts %d", kind, ts);
-      dev = km->pair_out; n = P;
-    }
-    else if (is(field, "pair_k")) {
-      DGR_REQUIRE(km->pair_k, "this build kept no pair_k for the '%s' map at ts %d", kind, ts);
-      dev = km->pair_k; n = P; eb = 2;
-    }
-    else if (is(field, "out_ptr")) { dev = km->out_ptr; n = cout.n_cap + 1; }
-    else if (is(field, "out_pos")) { dev = km->out_pos; n = P; }
-    else if (is(field, "in_ptr") || is(field, "in_pos")) {
-      DGR_REQUIRE(km->in_ptr && km->in_pos, "the '%s' map at ts %d has no in-major CSR", kind, ts);
-      if (is(field, "in_ptr")) { dev = km->in_ptr; n = cin.n_cap + 1; } else { dev = km->in_pos; n = P; }
-    }
-    else if (is(field, "pair_cap")) { scalar = true; value = km->pair_cap; }
-    else if (is(field, "n_cap")) { scalar = true; value = cout.n_cap; }
-    else if (is(field, "K")) { scalar = true; value = km->K; }
-    else DGR_REQUIRE(false, "no field '%s' in a kernel map", field);
-  } else if (is(kind, "nbr_same") || is(kind, "nbr_down") || is(kind, "nbr_up")) {
-    DGR_REQUIRE(is(kind, "nbr_same") || l < 3, "no such neighbour table at ts %d", ts);
-    const DgrNbrTable *t = is(kind, "nbr_same") ? &ms.nsame[l] : is(kind, "nbr_down") ? &ms.ndown[l] : &ms.nup[l];
-    DGR_REQUIRE(t->built, "this build made no '%s' table at ts %d", kind, ts);
-    if (is(field, "nbr")) { dev = t->nbr; n = t->n_pad * t->K; }
-    else if (is(field, "n_pad")) { scalar = true; value = t->n_pad; }
-    else if (is(field, "perm") || is(field, "cls_count") || is(field, "cls_cap")) {
-      DGR_REQUIRE(t->perm && t->cls_count, "the '%s' table at ts %d has no parity classes", kind, ts);
-      if (is(field, "perm")) { dev = t->perm; n = 8 * t->cls_cap; }
-      else if (is(field, "cls_count")) { dev = t->cls_count; n = 8; }
-      else { scalar = true; value = t->cls_cap; }
-    }
-    else DGR_REQUIRE(false, "no field '%s' in a neighbour table", field);
-  } else {
-    DGR_REQUIRE(false, "no kind '%s'", kind);
-  }
-  if (scalar) { n = 1; eb = 8; }
-  *count = n;
-  *elem_bytes = eb;
-  if (!host_out) return DGR_OK;
-  DGR_REQUIRE(capacity_bytes >= n * eb, "host buffer too small (%lld < %lld bytes)", (long long)capacity_bytes, (long long)(n * eb));
-  if (scalar) {
-    memcpy(host_out, &value, sizeof(int64_t));
-  } else if (n > 0) {
-    DGR_REQUIRE(dev, "field '%s' of '%s' at ts %d was not built", field, kind, ts);
-    DGR_HIP_CHECK(hipMemcpy(host_out, dev, (size_t)(n * eb), hipMemcpyDeviceToHost));
-  }
+  else
+    DGR_CHECK(build(ms->cm[0], ms->cm[0], conv1_ks, MAP_CONV1, 0, &ms->conv1));
+  for (int l = 0; l < 3; ++l) DGR_CHECK(build(ms->cm[l], ms->cm[l + 1], 3, MAP_DOWN, l, &ms->down[l]));
   return DGR_OK;
 }

@@ -860,7 +860,7 @@ int dgr_resunet_forward_impl(dgr_ctx *ctx, dgr_net *net, const int32_t *coords, 
   // dense neighbour tables (conv_os.hip).  Any other 3-D shape takes the rule-major two-phase path of conv.hip.
   const bool use_nbr = net->D == 3 && net->cin <= 8 && net->conv1_ks <= 7;
   f.wide3 = wide_coarse_mode(net, use_nbr, N);
-  DGR_CHECK(dgr_build_maps(A, coords, N, net->D, net->conv1_ks, &f.ms, stream, /*skip_conv1_map=*/use_nbr, /*lean=*/true, use_nbr, f.wide3));
+  DGR_CHECK(dgr_build_maps(A, coords, N, net->D, net->conv1_ks, &f.ms, stream, DgrMapsMode{true, use_nbr, f.wide3}));
   if (f.prof) {
     DGR_HIP_CHECK(hipEventRecord(m1, stream));
     (net->D == 3 ? ctx->map3_spans : ctx->map6_spans).push_back({m0, m1});
@@ -1044,7 +1044,7 @@ extern "C" int dgr_debug_conv_layer(dgr_ctx *ctx, dgr_net *net, int layer, const
   Fwd f;
   f.ctx = ctx; f.net = net; f.stream = stream; f.prof = false;
   f.ms.overflow = ctx->flag_dev;
-  DGR_CHECK(dgr_build_maps(A, coords, N, net->D, 3, &f.ms, stream, false, /*lean=*/true, /*nbr_tables=*/net->D == 3));
+  DGR_CHECK(dgr_build_maps(A, coords, N, net->D, 3, &f.ms, stream, DgrMapsMode{true, net->D == 3, false}));
   const int64_t n_cap = f.ms.cm[0].n_cap;
   if (!f.ms.use_nbr) DGR_ALLOC(f.ybuf, A, float, f.ms.same[0].pair_cap * L.cout);
   Tensor tin{const_cast<float *>(in), L.cin, in_relu}, tout{out, L.cout, 0};

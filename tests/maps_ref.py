@@ -16,7 +16,7 @@ LEVELS = (1, 2, 4, 8)
 TILE_M = 64            # DGR_TILE_M: pairs per MFMA tile
 OS_ROWS = 64           # DGR_OS_ROWS: the neighbour tables' row padding
 CAP_ROW_6D = 160       # reserved pairs per row of a 6-D map (dgr_build_maps: cap_row)
-# hit-list records a search wave may leave before the placing pass replays it (kmap.hip: KM_REGION = 512; the regions
+# hit-list records a search wave may leave before the placing pass replays it (kmap.hip: KM_REGION = 512, km_region_of; the regions
 # are KM_REGION / 2, and 2 * KM_REGION for the symmetric ts = 8 map).  The replay cases assert from these numbers that
 # they reach the replay: if KM_REGION changes, their preconditions fail in test_maps_ref_cpu.py.
 REGION_SYMMETRIC = 256        # KM_REGION / 2

@@ -301,11 +301,13 @@ def test_lines_cover_the_tile_edges():
 
 def test_region_constants_match_the_builder():
     """the replay preconditions rest on the hit-list region sizes: they are constants of the reference, tied to
-    KM_REGION of csrc/kmap.hip here so that a change of either fails loudly"""
+    KM_REGION and the rule km_region_of of csrc/kmap.hip here so that a change of either fails loudly"""
     import os
     import re
     from conftest import ROOT
     src = open(os.path.join(ROOT, 'deepglobalregistration_amd', 'csrc', 'kmap.hip')).read()
     region = int(re.search(r'constexpr int KM_REGION = (\d+);', src).group(1))
-    assert 'r.hl.region = (J.in->ts >= 8 && r.symmetric) ? 2 * KM_REGION : KM_REGION / 2;' in src
+    assert ('constexpr int km_region_of(int ts_in, bool symmetric) '
+            '{ return (ts_in >= 8 && symmetric) ? 2 * KM_REGION : KM_REGION / 2; }') in src
+    assert 'r.hl.region = km_region_of(J.in->ts, symmetric);' in src
     assert (ref.REGION_SYMMETRIC, ref.REGION_SYMMETRIC_TS8, ref.REGION_STRIDED) == (region // 2, 2 * region, region // 2)
