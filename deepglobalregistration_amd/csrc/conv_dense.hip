@@ -26,7 +26,7 @@
 //     channels of a 32-channel step to the matrix unit in another order (4 lq .. + 3 and 16 + 4 lq .. + 3 per lane),
 //     so the f32 sums inside one MFMA round differently (tests/test_gpu_dense_conv.py: 2e-6 of the unit-norm output).
 //   * input rows carry their largest |x| (bits, written by their producer's epilogue: out_amax below and in
-//     conv_os.hip / conv.hip) -- the row's power-of-two scale is dgr_row_scale_of of it; no separate scale pass.
+//     conv_os.hip / conv1.hip) -- the row's power-of-two scale is dgr_row_scale_of of it; no separate scale pass.
 //
 // What bounded it until round 4 (the round-3 reading "the gather rate of random rows" was
 // wrong: row order and occupancy change nothing): the LDS traffic of the loop -- every wave re-read the offset's 16 KB of

@@ -1,4 +1,4 @@
-// Native vector types of the conv family (conv.hip, conv_os.hip, conv_dense.hip, conv_up.hip, conv_wide.hip, split.h,
+// Native vector types of the conv family (conv.hip, conv_identity.hip, conv1.hip, conv_os.hip, conv_dense.hip, conv_up.hip, conv_wide.hip, split.h,
 // dense_tile.h): MFMA operands and accumulators, 16-byte loads and stores.  (Native vectors, not HIP's float4 / uint4
 // structs: those copy as memcpy and stay in scratch.)
 #pragma once

@@ -183,7 +183,7 @@ int dgr_build_maps(DgrArena &arena, const int32_t *coords, int64_t N, int D, int
                    DgrMapSet *ms, hipStream_t stream, DgrMapsMode mode);
 // per-offset pair counts of a neighbour table (statistics / tests; synchronises)
 int dgr_nbr_counts(const DgrNbrTable &t, const int32_t *n_out_dev, int64_t counts[27]);
-// conv1 fused with its neighbour search (D = 3, Cin <= 8, Cout = 32): no kernel map for the ks^3 offsets
+// conv1 fused with its neighbour search (conv1.hip; D = 3, Cin <= 8, Cout = 32): no kernel map for the ks^3 offsets
 int dgr_conv1_probe(DgrArena &arena, const DgrCoordMap &cm, int ks, const float *in, int in_ld, int cin,
                     const float *w_tiled, const float *shift, float *out, int out_ld, int32_t *pair_count,
                     hipStream_t stream, const float *w_compact = nullptr, const char **kernel_name = nullptr,
@@ -205,26 +205,56 @@ int dgr_exclusive_scan_multi(DgrArena &arena, int count, const int32_t *const *i
                              int32_t *const *total_out, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------
-// sparse convolution (conv.hip)
+// sparse convolution (conv.hip, conv_identity.hip, conv1.hip, conv_wide.hip, conv_os.hip, conv_dense.hip, conv_up.hip)
 // ------------------------------------------------------------------------------------------
+// Blocks of `kernel` (threads per block, bytes of dynamic LDS) that are resident at once on num_cus CUs (0: every CU of
+// the current device): its occupancy per CU, at least 1, times the CUs.  Two runtime queries: callers cache the figure.
+int dgr_resident_blocks(const void *kernel, int threads, size_t lds_bytes, int *blocks, int num_cus = 0);
 struct DgrConvLaunch {
   const float *in;  // [n_in, in_ld]
   int in_ld;
   int in_relu;  // apply max(x,0) when gathering
-  float *out;   // identity maps only: [n_out, out_ld] written directly (product + shift)
+  float *out;   // dgr_conv_identity_launch: [n_out, out_ld] written directly (product + shift); rule-major: the reduction's
   int out_ld;
   float *y;            // non-identity maps: per-pair product rows [pairs, cout]
   const float *shift;  // identity maps: per-channel shift (may be null)
   const float *w;  // MFMA-B-fragment tiled weights of this layer
   int cin, cin_pad, cout, cout_pad, K;
-  const int32_t *pair_in, *pair_out, *tile_ptr, *rule_ptr;  // nullptr pairs => identity map
+  const int32_t *pair_in, *pair_out, *tile_ptr, *rule_ptr;  // the kernel map's lists (identity convs: nullptr)
   const int4 *tile_desc;                                     // per-tile (k, first pair, count)
   const int32_t *n_rows_dev;                                 // identity map: number of rows
   int64_t tile_bound;                                        // host upper bound on the tile count (0 = unknown)
   int l2_normalize = 0;   // identity maps with Cout <= 32: rows leave as x / (|x|_2 + 1e-8) (model/resunet.py:643-647)
   unsigned long long *clk = nullptr;   // profiling: {earliest start, latest end} wall-clock ticks of the kernel (conv_wide.hip)
 };
+// ... as the kernels of conv.hip and conv_identity.hip take it (one record for both: the rule-major kernel still has
+// the identity mode that identity_conv_kernel replaced)
+struct ConvKArgs {
+  const float *in;
+  float *out;          // identity maps: written directly (acc + shift); otherwise unused
+  float *y;            // [pairs, y_ld] per-pair product rows
+  const float *shift;  // identity maps: folded bias / BN shift (may be null)
+  const float *w;
+  const int32_t *pair_in, *pair_out, *tile_ptr, *rule_ptr, *n_rows_dev;
+  const int4 *tile_desc;
+  int in_ld, out_ld, in_relu, y_ld;
+  int cin, cin_pad, cout, K;
+  int l2_normalize;    // identity maps, Cout <= 32 (one 32-channel block per row): x / (|x|_2 + 1e-8) on the way out
+};
+inline ConvKArgs dgr_conv_kargs(const DgrConvLaunch &a) {
+  ConvKArgs ka;
+  ka.in = a.in; ka.out = a.out; ka.w = a.w; ka.y = a.y; ka.shift = a.shift; ka.y_ld = a.cout;
+  ka.pair_in = a.pair_in; ka.pair_out = a.pair_out; ka.tile_ptr = a.tile_ptr; ka.rule_ptr = a.rule_ptr;
+  ka.n_rows_dev = a.n_rows_dev; ka.tile_desc = a.tile_desc;
+  ka.in_ld = a.in_ld; ka.out_ld = a.out_ld; ka.in_relu = a.in_relu;
+  ka.cin = a.cin; ka.cin_pad = a.cin_pad; ka.cout = a.cout; ka.K = a.K;
+  ka.l2_normalize = a.l2_normalize;
+  return ka;
+}
+// rule-major f32 product rows over a kernel map (conv.hip): pair_in must be set
 int dgr_conv_launch(const DgrConvLaunch &a, int num_cus, hipStream_t stream, const char **kernel_name = nullptr);
+// kernel-volume-1 conv over the rows of one map (conv_identity.hip): 64 -> <= 64 or 96 -> 33..64 channels, written to `out`
+int dgr_conv_identity_launch(const DgrConvLaunch &a, int num_cus, hipStream_t stream, const char **kernel_name = nullptr);
 // A tensor in the form the wide-layer kernel gathers (conv_wide.hip): per row channels / 64 blocks of 256 bytes
 // [h of 64 channels][m of the same] (two f16 pieces of scale * x, the consumer's pending ReLU applied) + the row's
 // power-of-two scale.  Written by the tensor's producer (dgr_reduce_rows) next to the f32 rows.
@@ -251,10 +281,11 @@ int dgr_split_rows(const float *in, int in_ld, int relu, const int32_t *n_dev, i
 int dgr_reduce_rows(const float *y, int cout, const int32_t *ptr, const int32_t *pos, const int32_t *n_dev,
                     int64_t n_cap, float *out, int out_ld, const float *shift, const float *res, int res_ld,
                     int res_relu, hipStream_t stream, const DgrSplitRows *split = nullptr, int out_relu = 0);
-// output-stationary conv for Cin <= 8, Cout == 32 (conv1): no product rows, no reduction pass
+// output-stationary conv for Cin <= 8, Cout == 32 (conv1, conv1.hip): no product rows, no reduction pass; w_quad = the
+// weights quad-major, required for (and only read with) six input channels
 int dgr_conv_small_cin(const float *in, int in_ld, int in_relu, int cin, const float *w_tiled, const float *w_quad,
                        const float *shift, const DgrKernelMap &km, const int32_t *n_out_dev, int64_t n_out_cap, float *out,
-                       int out_ld, hipStream_t stream);
+                       int out_ld, hipStream_t stream, const char **kernel_name = nullptr);
 // output-stationary fused conv (conv_os.hip): out[o] = shift (+ res[o]) + sum_k in[nbr[k][o]] W[k], ascending k,
 // accumulated in LDS -- no product rows, no reduction pass.  w16 = the layer's weights in 16x16x4 fragment order.
 struct DgrConvOsLaunch {

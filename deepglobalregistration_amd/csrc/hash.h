@@ -1,4 +1,4 @@
-// Coordinate hashing shared by every voxel table of the library (coordmap.hip, kmap.hip, conv.hip, voxelmean.hip,
+// Coordinate hashing shared by every voxel table of the library (coordmap.hip, kmap.hip, conv1.hip, voxelmean.hip,
 // tsdf.hip, tsdfmesh.hip): the hash, the look-ups, the ONE probe-and-claim loop and the host helper that sizes a table.
 // COO coordinates are int32 rows [batch, x_0 .. x_{D-1}] (NC = 1 + D ints).  The hash table is
 // open addressing with linear probing; entries are row indices (-1 = empty) into the coordinate

@@ -5,8 +5,8 @@
 //
 // Load time: eval-mode batch norm is folded into the kernels (scale) and a per-channel shift; the
 // kernels are re-tiled on the device into the MFMA B-operand order documented in conv.hip.
-// Forward: a loop over the layer table; every conv is one of the kernel families of conv.hip / conv_os.hip /
-// conv_wide.hip (chosen per layer in layer_kind); rule-major layers write per-pair product rows that a deterministic reduction sums on top of the folded
+// Forward: a loop over the layer table; every conv is one of the kernel families of conv.hip / conv_identity.hip /
+// conv1.hip / conv_os.hip / conv_wide.hip (chosen per layer in layer_kind); rule-major layers write per-pair product rows that a deterministic reduction sums on top of the folded
 // shift (+ residual).  ReLU is never a separate pass: a tensor carries a "ReLU pending" flag and the consumer applies
 // max(x,0) while gathering (or the producer bakes it into the split rows it writes for a wide-layer consumer).
 // ME.cat is free: producers write into column ranges of a pre-concatenated buffer (row stride = total channels).
@@ -74,15 +74,15 @@ static_assert(N_LAYERS == 23, "ResUNetBN2C has 23 convs");
 // Which kernel runs a layer (layer_kind, the one place that decides it)
 enum Kind : int {
   K_NONE,         // no forward yet
-  K_CONV1_FUSED,  // conv1 fused with its neighbour search (dgr_conv1_probe)
-  K_SMALL_CIN,    // conv1 with Cin <= 8, output-stationary over the rule-major map (conv.hip)
+  K_CONV1_FUSED,  // conv1 fused with its neighbour search (dgr_conv1_probe, conv1.hip)
+  K_SMALL_CIN,    // conv1 with Cin <= 8, output-stationary over the rule-major map (conv1.hip)
   K_RULE,         // rule-major f32 product rows + reduction (conv.hip)
   K_WIDE,         // rule-major product rows from split rows, f16x2 (conv_wide.hip) + reduction
   K_OS_F32,       // output-stationary over neighbour tables, list-based, f32 operands (conv_os.hip)
   K_OS,           // the same with split operands
   K_DENSE,        // dense tiles (conv_dense.hip)
   K_UP,           // transposed conv by parity class (conv_up.hip)
-  K_IDENTITY};    // kernel volume 1 (conv.hip)
+  K_IDENTITY};    // kernel volume 1 (conv_identity.hip)
 static bool on_tables(Kind k) { return k == K_OS_F32 || k == K_OS || k == K_DENSE || k == K_UP; }
 static bool reads_amax(Kind k) { return k == K_OS || k == K_DENSE || k == K_UP; }
 static bool writes_amax(Kind k) { return k == K_CONV1_FUSED || on_tables(k); }   // (their epilogues can)
@@ -428,7 +428,7 @@ static int make_layer(dgr_net *net, WeightPrep &P, const dgr_weight_desc *descs,
     }
   }
   if (net->D == 3 && name == "conv1" && cin == 1 && cout == 32 && K <= 343) {
-    // conv1_grid_mfma (conv.hip): per z-slab kz and 4-offset step s the A operands of the two v_mfma_f32_16x16x4_f32,
+    // conv1_grid_mfma (conv1.hip): per z-slab kz and 4-offset step s the A operands of the two v_mfma_f32_16x16x4_f32,
     // wt[kz][s][lane] = {W[k][lane & 15], W[k][16 + (lane & 15)]}, k = kz ks^2 + 4 s + (lane >> 4); zero past the slab
     int ks = 1;
     while (ks * ks * ks < K) ++ks;
@@ -445,7 +445,7 @@ static int make_layer(dgr_net *net, WeightPrep &P, const dgr_weight_desc *descs,
     }));
   }
   if (name == "conv1" && cin == 6 && cout == 32 && K > 1) {
-    // conv_cin6_quad_kernel (conv.hip): wq[k][i][q][e] = W[k][i / 2][8 q + 4 (i % 2) + e], batch norm folded in
+    // conv_cin6_quad_kernel (conv1.hip): wq[k][i][q][e] = W[k][i / 2][8 q + 4 (i % 2) + e], batch norm folded in
     const int64_t ne = (int64_t)K * 192;
     DGR_CHECK(W.alloc(&L.wq, ne));
     float *const dst = L.wq;
@@ -604,7 +604,7 @@ static Kind layer_kind(const DgrMapSet &ms, bool wide3, const DgrLayer &L, const
     if (tiles && m.map == M_UP && m.nbr->perm && !has_res && dgr_conv_up_supported(L.cin, L.cin_pad, L.cout)) return K_UP;
     return split ? K_OS : K_OS_F32;
   }
-  // (Cin = 6 / 1 -- the inlier net's two input widths -- run the thread-per-voxel variant, conv.hip)
+  // (Cin = 6 / 1 -- the inlier net's two input widths -- have kernels of their own: dgr_conv_small_cin, conv1.hip)
   if (!m.swapped && !has_res && L.cin <= 8 && L.cout == 32 && L.cin_pad == 8) return K_SMALL_CIN;
   return L.wb ? K_WIDE : K_RULE;
 }
@@ -631,7 +631,7 @@ static int run_layer(dgr_ctx *ctx, const dgr_net *net, int li, hipStream_t strea
       break;
     case K_SMALL_CIN:
       DGR_CHECK(dgr_conv_small_cin(a.in, a.in_ld, a.in_relu, L.cin, L.w, L.wq, L.shift, r.km, r.n_out, r.n_out_cap, a.out,
-                                   a.out_ld, stream));
+                                   a.out_ld, stream, kname));
       break;
     case K_WIDE: {
       DgrConvLaunch ac = a;
@@ -639,7 +639,8 @@ static int run_layer(dgr_ctx *ctx, const dgr_net *net, int li, hipStream_t strea
       DGR_CHECK(dgr_conv_wide_launch(ac, r.split_in, L.wb, L.wb_piece, L.w_unscale, ctx->num_cus, stream, kname));
       break;
     }
-    case K_RULE: case K_IDENTITY: DGR_CHECK(dgr_conv_launch(a, ctx->num_cus, stream, kname)); break;
+    case K_RULE: DGR_CHECK(dgr_conv_launch(a, ctx->num_cus, stream, kname)); break;
+    case K_IDENTITY: DGR_CHECK(dgr_conv_identity_launch(a, ctx->num_cus, stream, kname)); break;
     case K_OS_F32: case K_OS: case K_DENSE: case K_UP: DGR_CHECK(dgr_conv_os_launch(r.os, stream, kname)); break;
     default: DGR_REQUIRE(false, "layer %s: not launched yet", L.name.c_str());
   }
@@ -684,7 +685,7 @@ struct Fwd {
                 L.name.c_str());
     DGR_REQUIRE(kind == K_DENSE || (!in.dsplit_only && !out.dsplit_only), "layer %s: dense split rows outside the dense-tile kernel", L.name.c_str());
     // the default names: of the kinds whose launch reports none of its own
-    const char *kname = (L.cin == 6 && L.wq) ? "conv_cin6_quad_kernel" : L.cin == 1 ? "conv_small_cin_row_kernel" : "conv_small_cin_kernel";
+    const char *kname = "";
     if (kind == K_CONV1_FUSED) {
       kname = "conv1_grid_kernel";
       r.cm0 = cin_map;

@@ -1,6 +1,6 @@
 // The two-f16-piece split of f32 operands and the row maximum its scale comes from, shared by every split-operand conv
 // kernel (conv_wide.hip, conv_os.hip, and through dense_tile.h conv_dense.hip / conv_up.hip) and by the producers of
-// their inputs (reduce_rows and the conv1 epilogues in conv.hip, the epilogues of conv_os.hip and dense_tile.h, the
+// their inputs (reduce_rows in conv.hip, the conv1 epilogues in conv1.hip, the epilogues of conv_os.hip and dense_tile.h, the
 // "dense split rows" of conv_dense.hip): one definition, so that a row split by its producer is bit-identical to the
 // same row split by a consumer.
 #pragma once

@@ -38,6 +38,22 @@ def test_fcgf_forward_matches_oracle(ks):
     assert len(stats) == 23 and stats[0]['K'] == ks ** 3 and stats[-1]['K'] == 1
 
 
+def test_3d_net_with_conv1_size_9_on_the_generic_small_cin_kernel():
+    """A 3-D net with a conv1 size above 7 has a rule-major map for its 729 offsets, and with five input channels conv1
+    runs the generic output-stationary kernel (conv1.hip) on it.  Most rows have dozens of pairs here: the kernel's rounds of
+    eight pairs and its tail both run (the 6-D rows of the test below have at most five pairs, the tail alone), and
+    channel 4 reads the second 4-channel block of the tiled weights."""
+    rng = np.random.default_rng(45)
+    coords = np.concatenate([random_cloud_coords(rng, 700, 12, 3, batch=b) for b in (0, 1)])
+    same = coords[:, None, 0] == coords[None, :, 0]
+    pairs = (same & (np.abs(coords[:, None, 1:] - coords[None, :, 1:]).max(-1) <= 4)).sum(1)
+    assert (pairs >= 16).mean() > 0.8 and (pairs % 8 != 0).any() and (pairs < 8).any(), np.bincount(pairs)
+    feats = rng.standard_normal((len(coords), 5)).astype(np.float32)
+    net, _, _ = _check(3, 5, 16, 9, False, coords, feats, seed=8)
+    first = _first_kernel(net, coords, feats)
+    assert first == 'conv_small_cin_kernel', first
+
+
 @pytest.mark.parametrize('n', [1, 2, 7, 40, 300])
 def test_fcgf_forward_on_tiny_clouds_with_negative_coordinates(n):
     """Edge cases of the parity-class row lists of the transposed convs (conv_up.hip; round 6): clouds so small that
@@ -94,14 +110,52 @@ def test_3d_net_on_the_rule_major_path():
     assert not any('sparse_conv_os' in k or 'conv1_grid' in k for k in kinds) and any('sparse_conv_mfma_v2' in k for k in kinds)
 
 
+def _first_kernel(net, coords, feats):
+    """Name of the kernel that ran conv1 in one profiled forward."""
+    from deepglobalregistration_amd import ops
+    ops.set_profiling('cuda', True)
+    net.forward(torch.from_numpy(coords).cuda(), torch.from_numpy(feats).cuda())
+    kinds = ops.conv_launch_kinds('cuda')
+    ops.set_profiling('cuda', False)
+    return kinds[0]
+
+
+@pytest.mark.parametrize('cin,cin_pad', [(10, 32), (33, 64)])
+def test_3d_net_conv1_with_unaligned_input_width(cin, cin_pad):
+    """conv1 of a rule-major 3-D net whose input width is no multiple of 4: the caller's rows cannot be gathered in
+    16-byte pieces, so the layer runs the element-wise gather of the rule-major kernel (VEC = false, conv.hip), zero-padded
+    to the 32 or 64 input channels the kernel is built for."""
+    rng = np.random.default_rng(43)
+    coords = np.concatenate([random_cloud_coords(rng, 2000, 16, 3, batch=b) for b in (0, 1)])
+    feats = rng.standard_normal((len(coords), cin)).astype(np.float32)
+    net, _, _ = _check(3, cin, 16, 3, False, coords, feats, seed=6)
+    first = _first_kernel(net, coords, feats)
+    assert first.startswith('sparse_conv_mfma_v2<%d, 2, 1, 1, 1, false>' % cin_pad), first
+
+
+def _rows_6d(rng, n):
+    # 6-D rows built like the pipeline does: unique 3-D voxel + a second 3-D voxel
+    c0 = random_cloud_coords(rng, n, 12, 3)
+    c1 = c0[:, 1:] + rng.integers(-2, 3, (len(c0), 3)).astype(np.int32)
+    return np.concatenate([c0, c1], axis=1).astype(np.int32)
+
+
 def test_inlier_net_6d_forward_matches_oracle():
     rng = np.random.default_rng(7)
-    # 6-D rows built like the pipeline does: unique 3-D voxel + a second 3-D voxel
-    c0 = random_cloud_coords(rng, 1600, 12, 3)
-    c1 = c0[:, 1:] + rng.integers(-2, 3, (len(c0), 3)).astype(np.int32)
-    coords = np.concatenate([c0, c1], axis=1).astype(np.int32)
+    coords = _rows_6d(rng, 1600)
     feats = np.cos(rng.uniform(-3, 3, (len(coords), 6))).astype(np.float32)
     _check(6, 6, 1, 3, False, coords, feats, seed=11)
+
+
+def test_6d_net_with_three_input_channels_on_the_generic_small_cin_kernel():
+    """Input widths other than the inlier net's own (6: the quad kernel, 1: a thread per voxel) run conv1 on the generic
+    output-stationary kernel, 32 lanes per voxel (conv1.hip)."""
+    rng = np.random.default_rng(7)
+    coords = _rows_6d(rng, 1600)
+    feats = np.cos(rng.uniform(-3, 3, (len(coords), 3))).astype(np.float32)
+    net, _, _ = _check(6, 3, 1, 3, False, coords, feats, seed=11)
+    first = _first_kernel(net, coords, feats)
+    assert first == 'conv_small_cin_kernel', first
 
 
 def test_row_permutation_equivariance_full_size():

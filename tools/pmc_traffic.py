@@ -3,8 +3,8 @@
     python tools/pmc_traffic.py fetch_results.db write_results.db > profiles/rNN_conv_hbm_traffic.json
 FETCH_SIZE / WRITE_SIZE are in KB; on gfx950 FETCH_SIZE reads 1/2 of the bytes of wide coalesced reads
 (MI355X_MICROARCH.md, HBM section) -> fetch bytes = 2 x FETCH_SIZE x 1024; WRITE_SIZE is used as is.
-A "conv launch" is one layer launch (MFMA kernel, small-Cin kernel or fused conv1); its reduce pass is
-counted into the same launch."""
+A "conv launch" is one layer launch (the MFMA kernel of conv.hip, the identity conv of conv_identity.hip, a small-Cin
+kernel or the fused conv1 of conv1.hip); its reduce pass is counted into the same launch."""
 import json
 import sqlite3
 import sys
